@@ -2,7 +2,7 @@
 """Hot-path benchmark (see DESIGN.md "Measurement").
 
     python bench.py --gpus N --steps K --warmup W [--config C] [--batch B] [--dtype bf16|fp32|fp8]
-                    [--mode train|sample]
+                    [--mode train|sample] [--dump-outputs DIR] [--full]
 
 Workloads (`--config`, values restated in slotdiffusion_amd/configs.py), bf16 storage / fp32 accumulate,
 synthetic data, seeded random weights (zero-initialised layers replaced by small random values so no
@@ -20,8 +20,19 @@ backward, gradient all-reduce (N > 1), global-norm clip, Adam.  value = N * imag
 [images/s; a clip counts its frames], whole job.  mode=sample: one 20-NFE DPM-Solver++ sampling pass over
 the batch's slots (20 x (UNet eps + x0 conversion + VQ quantise) + solver updates); value = N * images *
 20 * K / seconds.  Inputs are resident in HBM; for N > 1 every rank works on its own batch (weak
-scaling), time is the max over ranks between barriers.
-Extra JSON objects: `roofline` (MFMA, dominant kernel family sdmi_igemm) and `roofline_hbm` (GroupNorm
+scaling), time is the max over ranks between barriers.  ms_per_step = milliseconds of one timed step (one
+optimiser step / one 20-NFE pass); --steps K is the number of timed steps.
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step as float32
+DIR/<name>.npy -- mode=train: `loss`, and the same fixed, seeded sample of 4 Mi elements of the trainable
+range of the updated parameter arena (`params`) and of the step's gradient arena (`grads`); mode=sample:
+the final latents `latents` [B, 3, h, w].  Same arguments -> same inputs, so two builds compare output
+for output.
+A plain run does only the headline: set-up, warm-up, the K timed steps, the outputs, the result line
+(`denoise`, `denoise_big_batch` and `comm` are null).  --full adds everything else, each leg still
+switchable off by its --no-* / --big-batch 0 / --only-train flag: the sampling leg of mode=train
+(`denoise`), the big-batch sampling figure, the exchange timings of N > 1 (`comm`), one more step behind
+the timed loop whose loss / parameters / latents the finite check reads, and the objects below.
+Extra JSON objects (--full): `roofline` (MFMA, dominant kernel family sdmi_igemm) and `roofline_hbm` (GroupNorm
 family) for the timed step, `denoise.roofline` for the sampling leg: algorithmic flops / bytes per
 launch counted from the launch arguments, durations from a rocprofv3 --kernel-trace of THIS command's
 graph-replayed timed region (child runs on the same box, see replayed_trace(); falls back to a live eager
@@ -34,7 +45,6 @@ import json
 import os
 
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC (RCCL across processes)
-os.environ.setdefault('DEBUG_HIP_FORCE_GRAPH_QUEUES', '2')  # = slotdiffusion_amd.configure_runtime(), before HIP starts
 import sys
 import time
 
@@ -45,6 +55,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {'bf16': 2500.0, 'fp32': 157.3, 'fp8': 5000.0}      # MI355X dense MFMA peaks (MI355X_MICROARCH.md)
 CPU_THREADS = 64       # cpu_baseline: fixed thread count, pinned to the first cores (repeatable across boxes)
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: elements kept of an arena (2 x 16 MB in float32)
 
 
 def build_model(dtype, seed=1234, config='clevrtex128'):
@@ -72,6 +83,22 @@ def synth_batch(B, rank, device, res=128, frames=None):
     g = torch.Generator().manual_seed(1234 + rank)
     shape = (B, 3, res, res) if not frames else (B, frames, 3, res, res)
     return (torch.randn(shape, generator=g) * 0.5).clamp(-1, 1).to(device)
+
+
+def arena_sample(n, device):
+    """--dump-outputs: sorted indices of a fixed, seeded sample of an n-element arena (None: all of it)."""
+    if n <= DUMP_SAMPLE:
+        return None
+    g = torch.Generator().manual_seed(0)
+    return torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values.to(device)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one float32 <path>/<name>.npy per array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def cpu_baseline(model, cfg, mode, quick=False):
@@ -385,10 +412,17 @@ def main():
                     help='profiling aid: skip the sampling leg of --mode train')
     ap.add_argument('--mark', action='store_true',
                     help='internal (replayed_trace): bracket the timed region with marker kernels')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and check beyond the headline figure: sampling leg of --mode train, big-batch sampling, '
+                         'exchange timings (N > 1), one more checked step, roofline / PMC child passes, CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
-    # --gpus N is the number of ranks (one per GPU).  Started without a launcher it re-executes
-    # itself under `python -m torch.distributed.run --nproc-per-node N` (the reference's launch:
+    # --gpus N is the number of ranks (one per GPU).  Started without a launcher it runs itself
+    # again in a child `python -m torch.distributed.run --nproc-per-node N` (the reference's launch:
     # torch.distributed.launch --nproc_per_node=$GPUS, scripts/sbatch_run.sh:36-39); a mismatch
     # between --gpus and the world the launcher set up, or fewer visible devices than ranks, is an
     # error -- never a silent single-GPU measurement.
@@ -453,6 +487,7 @@ def main():
             metrics._sqerr(torch.zeros(1, 8, device=dev), torch.ones(1, 8, device=dev))
 
     def timed(fn, steps, warmup, marked=False):
+        """-> (seconds of the `steps` timed calls, what the last of them returned)."""
         for _ in range(warmup):
             fn()
         if marked:
@@ -460,7 +495,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            res = fn()
         barrier()
         dt = time.perf_counter() - t0
         if marked:
@@ -469,49 +504,55 @@ def main():
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt)
-        return dt
+        return dt, res
 
-    # ---- sampling leg: 20-NFE DPM-Solver++ over the batch's slots ------------------------
-    model.eval()
-    with torch.no_grad():
-        slots, _ = model.encode(img)
-        if frames:
-            slots = slots.flatten(0, 1).contiguous()          # every frame's slots condition one latent
-        g = torch.Generator(device='cpu').manual_seed(77 + rank)
-        x_T = ops.nchw_to_nhwc(torch.randn(n_img, 3, lat, lat, generator=g).to(dev), torch.float32, 4)
+    dump = {}           # --dump-outputs: what the timed path computed in its last step
 
-        def sample_step():
-            return model._dpm_sample(x_T, slots)[0]
-        skip_sample = args.only_train and args.mode == 'train'
-        n_s = args.steps if args.mode == 'sample' else max(2, args.steps // 2)
-        dt_s = timed((lambda: None) if skip_sample else sample_step, n_s,
-                     args.warmup if args.mode == 'sample' else 1, marked=args.mode == 'sample')
-        denoise_rate = world * n_img * nfe * n_s / dt_s
-        # the timed configuration's result must at least be finite: final latents of one more pass
-        sample_finite = None
-        if not skip_sample:
-            z_fin = sample_step()
+    # ---- sampling leg: 20-NFE DPM-Solver++ over the batch's slots (mode=train: with --full only) ----
+    skip_sample = args.mode == 'train' and (args.only_train or not args.full)
+    denoise_rate = dt_s = n_s = sample_finite = sample_absmax = big_rate = None
+    if not skip_sample:
+        model.eval()
+        with torch.no_grad():
+            slots, _ = model.encode(img)
+            if frames:
+                slots = slots.flatten(0, 1).contiguous()          # every frame's slots condition one latent
+            g = torch.Generator(device='cpu').manual_seed(77 + rank)
+            x_T = ops.nchw_to_nhwc(torch.randn(n_img, 3, lat, lat, generator=g).to(dev), torch.float32, 4)
+
+            def sample_step():
+                return model._dpm_sample(x_T, slots)[0]
+            n_s = args.steps if args.mode == 'sample' else max(2, args.steps // 2)
+            dt_s, z_fin = timed(sample_step, n_s, args.warmup if args.mode == 'sample' else 1,
+                                marked=args.mode == 'sample')
+            denoise_rate = world * n_img * nfe * n_s / dt_s
+            if args.mode == 'sample' and args.dump_outputs:
+                dump['latents'] = ops.nhwc_to_nchw(z_fin, 3)
+            # the timed configuration's result must at least be finite: final latents of the last
+            # timed pass (--full: of one more pass)
+            if args.full:
+                z_fin = sample_step()
             sample_finite = bool(torch.isfinite(z_fin.float()).all())
             sample_absmax = float(z_fin.float().abs().max())
-        big_rate = None
-        if args.big_batch and args.big_batch != n_img and world == 1 and not args.only_train and \
-                args.config == 'clevrtex128' and args.mode == 'train':
-            # informational: the same sampler at a batch that fills the chip better
-            Bb = args.big_batch
-            slots_b = slots[:1].expand(Bb, -1, -1).contiguous() + 0.01 * torch.randn(
-                Bb, slots.shape[1], slots.shape[2], device=dev)
-            xT_b = ops.nchw_to_nhwc(torch.randn(Bb, 3, lat, lat, device=dev), torch.float32, 4)
-            big = lambda: model._dpm_sample(xT_b, slots_b)[0]
-            dt_b = timed(big, 2, 1)
-            big_rate = Bb * nfe * 2 / dt_b
-            model._graph_cache.clear()
-            del slots_b, xT_b
+            if args.full and args.big_batch and args.big_batch != n_img and world == 1 and not args.only_train and \
+                    args.config == 'clevrtex128' and args.mode == 'train':
+                # informational: the same sampler at a batch that fills the chip better
+                Bb = args.big_batch
+                slots_b = slots[:1].expand(Bb, -1, -1).contiguous() + 0.01 * torch.randn(
+                    Bb, slots.shape[1], slots.shape[2], device=dev)
+                xT_b = ops.nchw_to_nhwc(torch.randn(Bb, 3, lat, lat, device=dev), torch.float32, 4)
+                big = lambda: model._dpm_sample(xT_b, slots_b)[0]
+                dt_b, _ = timed(big, 2, 1)
+                big_rate = Bb * nfe * 2 / dt_b
+                model._graph_cache.clear()
+                del slots_b, xT_b
 
     # ---- training leg: forward + loss + backward (+ DDP all-reduce) + clip + Adam --------
-    model.train()
-    opt = FusedAdam(model, lr=1e-4, dec_lr=2e-4, clip_grad=bc['clip_grad'], total_steps=100000)
-    garena = model.grad_arena()
-    reducer = parallel.GradReducer(garena, world, wire) if dist is not None else None
+    if args.mode == 'train' or args.full:       # (a plain mode=sample run needs no optimiser state)
+        model.train()
+        opt = FusedAdam(model, lr=1e-4, dec_lr=2e-4, clip_grad=bc['clip_grad'], total_steps=100000)
+        garena = model.grad_arena()
+        reducer = parallel.GradReducer(garena, world, wire) if dist is not None else None
 
     def train_step(reduce=True):
         opt.zero_grad()
@@ -539,23 +580,31 @@ def main():
             graphed = GraphedTrainStep(model, opt, dict(img=img),
                                        allreduce=(True if dist is not None else None), world=world, wire=wire)
             run_step = lambda: graphed(dict(img=img))
-        dt_t = timed(run_step, args.steps, args.warmup, marked=True)
+        dt_t, last = timed(run_step, args.steps, args.warmup, marked=True)
         train_rate = world * n_img * args.steps / dt_t
-        # loss of the last timed step (the graphed step keeps it in a static tensor) + a finite check of the
-        # updated parameters: a fast step that produces NaN is not a measurement
-        last = run_step()
+        if args.dump_outputs:
+            # the loss of the last timed step, and the trainable range of the parameters it updated and of its
+            # gradients (the same sampled elements of both)
+            n_train = model.arena_ranges()[1]
+            idx = arena_sample(n_train, dev)
+            pick = lambda a: (a[:n_train] if idx is None else a[idx]).clone()
+            dump.update(loss=last.detach().reshape(1).clone(), params=pick(model.arena()), grads=pick(garena))
+        # loss of the last timed step (the graphed step keeps it in a static tensor; --full: of one more step) + a finite
+        # check of the updated parameters: a fast step that produces NaN is not a measurement
+        if args.full:
+            last = run_step()
         train_loss = float(graphed.loss if not args.no_graph else last)
         params_finite = bool(torch.isfinite(model.arena()).all())
-        if dist is not None:
+        if dist is not None and args.full:
             # the exchange by itself (all ranks idle otherwise) and what of it the step exposes:
             # the same graphed step without the collective, timed the same way
             def only_reduce():
                 reducer.reduce_all(4)
-            dt_ar = timed(only_reduce, 3, 1)
+            dt_ar, _ = timed(only_reduce, 3, 1)
             dt_nored = None
             if not args.no_graph:
                 nored = GraphedTrainStep(model, opt, dict(img=img), allreduce=None, world=world)
-                dt_nored = timed(lambda: nored(dict(img=img)), args.steps, 1)
+                dt_nored, _ = timed(lambda: nored(dict(img=img)), args.steps, 1)
             comm = {'rccl_ranks': dist.get_world_size(), 'backend': dist.get_backend(),
                     'devices': [f'cuda:{i}' for i in range(world)],
                     'grad_dtype_on_wire': wire,
@@ -589,24 +638,25 @@ def main():
                    'hip_graph': not args.no_graph, 'parallelism': f'dp{world}'},
         'denoise_big_batch': ({'value': big_rate, 'unit': 'image-denoise-steps/s',
                                'batch': args.big_batch} if big_rate else None),
-        'denoise': {'value': denoise_rate, 'unit': 'image-denoise-steps/s',
-                    'ms_per_20nfe_pass': 1e3 * dt_s / n_s, 'nfe': nfe, 'images': n_img},
+        'denoise': None if skip_sample else {
+            'value': denoise_rate, 'unit': 'image-denoise-steps/s', 'ms_per_20nfe_pass': 1e3 * dt_s / n_s, 'nfe': nfe,
+            'images': n_img, 'finite': sample_finite, 'latent_absmax': sample_absmax},
         'comm': comm,
     }
-    if skip_sample:
-        out['denoise'] = None
-    else:
-        out['denoise']['finite'] = sample_finite
-        out['denoise']['latent_absmax'] = sample_absmax
     if args.mode == 'train':
         out['loss'] = train_loss
         out['finite'] = bool(params_finite and train_loss == train_loss and abs(train_loss) != float('inf'))
     else:
         out['finite'] = sample_finite
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, dump)
+    del dump
 
-    # ---- rank-0-only instrumentation: no collective inside -------------------------------
-    argv0 = [a for a in sys.argv[1:] if a != '--mark']
-    argv0 = [a for i, a in enumerate(argv0) if a != '--mode' and (i == 0 or argv0[i - 1] != '--mode')]
+    # ---- rank-0-only instrumentation (--full): no collective inside ---------------------
+    # (the child passes neither dump outputs nor take the mode of this run)
+    argv0 = [a for a in sys.argv[1:] if a != '--mark' and not a.startswith('--dump-outputs=')]
+    argv0 = [a for i, a in enumerate(argv0) if a not in ('--mode', '--dump-outputs') and
+             (i == 0 or argv0[i - 1] not in ('--mode', '--dump-outputs'))]
 
     def roofline_of(mode, step_fn, steps, ms_step, want_hbm):
         """Roofline objects of one leg (see the module docstring)."""
@@ -745,7 +795,7 @@ def main():
         rf['traffic_dispatches'] = n_disp
         rf['traffic_ratio_to_algorithmic'] = (rf['traffic'] / rf['algorithmic_bytes_per_launch']) if rf['traffic'] else None
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         if args.mode == 'train':
             rf, hbm, summ = roofline_of('train', lambda: train_step(reduce=False), args.steps, ms, True)
             if world == 1 and not args.no_graph and not args.no_pmc:
@@ -772,7 +822,7 @@ def main():
                 out['roofline_hbm'] = hbm
             out['kernel_breakdown_ms'] = {k: round(v['ms'], 3) for k, v in
                                           sorted(summ.items(), key=lambda kv: -kv[1]['ms'])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(model, cfg, args.mode) if args.config == 'clevrtex128' else None
     if dist is not None:
         dist.barrier()

@@ -159,7 +159,7 @@ __device__ __forceinline__ void st_rows_to_y(const f32x4 (&x)[NSL][TT], lds_char
 }
 
 template <int C, int TT, int NSL>
-__device__ __forceinline__ void st_rows_store(const f32x4 (&x)[NSL][TT], bf16_t* gout, int ld, int w, int l15, int lg) {
+__device__ __forceinline__ void st_store_rows(const f32x4 (&x)[NSL][TT], bf16_t* gout, int ld, int w, int l15, int lg) {
 #pragma unroll
   for (int s = 0; s < NSL; ++s) {
     const int n0 = (w * NSL + s) * 16 + 4 * lg;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(512) void st_train_a_kernel(SdmiStTrainArgs p) {
     for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[s][tt][j] += ev0[s][j];
-  st_rows_store<C, TT, NSL>(acc, (bf16_t*)p.tok + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.tok + row0 * C, C, w, l15, lg);
   // ---- LayerNorm1 -> n1 (operand buffer + global), statistics
   st_layernorm_rows<C, TT, NSL>(acc, evg, evb, p.ln_eps, Y, lnred, (bf16_t*)p.n1 + row0 * C, p.st1 + row0 * 2, w, l15, lg);
 
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(512) void st_train_a_kernel(SdmiStTrainArgs p) {
     st_gemm_step<D, NSL, false, NSL * TT, TT>(rg, Y, yaddr, 0, 16 * PITCH, woff, acc, sx, sxx);   // (EXTRA: the stores / loads just issued stay outstanding)
 #pragma unroll
     for (int kt = 1; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-    st_rows_store<C, TT, NSL>(acc, (bf16_t*)p.qkv + row0 * 3 * C + pass * C, 3 * C, w, l15, lg);
+    st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.qkv + row0 * 3 * C + pass * C, 3 * C, w, l15, lg);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may outlive the workgroup's LDS
 }
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
       res[s][tt][2] = acc[s][tt][2] + ev0[s][2] + __uint_as_float(t2.y << 16);
       res[s][tt][3] = acc[s][tt][3] + ev0[s][3] + __uint_as_float(t2.y & 0xffff0000u);
     }
-  st_rows_store<C, TT, NSL>(res, (bf16_t*)p.x1 + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(res, (bf16_t*)p.x1 + row0 * C, C, w, l15, lg);
   st_layernorm_rows<C, TT, NSL>(res, evg, evb, p.ln_eps, Y, lnred, (bf16_t*)p.n2 + row0 * C, p.st2 + row0 * 2, w, l15, lg);
 
   // ---- slot cross-attention: q2 = n2 Wq2^T ; per (row, head): softmax over the slots ; a2
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
     for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) res[s][tt][j] += acc[s][tt][j] + ev0[s][j];
-  st_rows_store<C, TT, NSL>(res, (bf16_t*)p.x2 + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(res, (bf16_t*)p.x2 + row0 * C, C, w, l15, lg);
   st_layernorm_rows<C, TT, NSL>(res, evg, evb, p.ln_eps, Y, lnred, (bf16_t*)p.n3 + row0 * C, p.st3 + row0 * 2, w, l15, lg);
 
   // ---- GEGLU feed-forward, hidden chunk by hidden chunk: h = n3 W1^T + b1 ; g = value * gelu(gate) ; acc += g Wff2^T
@@ -999,7 +999,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_b1_kernel(SdmiStTrainBwdArgs
   st_gemm_step<D, NSL, false, NSL * TT, TT>(rg, Y, yaddr, 0, 16 * PITCH, woff, acc, sx, sxx);   // (EXTRA: the stores / loads just issued stay outstanding)
 #pragma unroll
   for (int kt = 1; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-  st_rows_store<C, TT, NSL>(acc, (bf16_t*)p.da2 + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.da2 + row0 * C, C, w, l15, lg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_b2_kernel(SdmiStTrainBwdArgs
   st_gemm_step<D, NSL, false, NSL * TT, TT>(rg, Y, yaddr, 0, 16 * PITCH, woff, acc, sx, sxx);   // (EXTRA: the stores / loads just issued stay outstanding)
 #pragma unroll
   for (int kt = 1; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-  st_rows_store<C, TT, NSL>(acc, (bf16_t*)p.da1 + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.da1 + row0 * C, C, w, l15, lg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -1074,7 +1074,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_a_kernel(SdmiStTrainBwdArgs 
   st_gemm_step<D, NSL, false, NSL * TT, TT>(rg, Y, yaddr, 0, 16 * PITCH, woff, acc, sx, sxx);   // (EXTRA: the stores / loads just issued stay outstanding)
 #pragma unroll
   for (int kt = 1; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-  st_rows_store<C, TT, NSL>(acc, (bf16_t*)p.dhgn + row0 * C, C, w, l15, lg);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.dhgn + row0 * C, C, w, l15, lg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 

@@ -49,11 +49,6 @@ class Method:
                  use_fp16=False):
         self.model, self.datamodule, self.params = model, datamodule, params
         self.ckp_path, self.local_rank, self.use_ddp = ckp_path, local_rank, use_ddp
-        from . import configure_runtime
-        # effective when the method is built before the first device call; INTEGRATION.md: call
-        # slotdiffusion_amd.configure_runtime() before build_model(...).cuda() -- one warning when it is too late
-        configure_runtime(warn=not getattr(Method, '_warned_runtime', False))
-        Method._warned_runtime = True
         if use_fp16:                      # the reference's --fp16 switch = our bf16 compute path
             model.set_compute_dtype('bf16')
         self.world = torch.distributed.get_world_size() if use_ddp else 1

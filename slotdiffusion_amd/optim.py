@@ -192,8 +192,6 @@ class GraphedTrainStep:
                  loss_weight=1.0, world=None, wire=None):
         self.model, self.opt, self.allreduce = model, opt, allreduce
         self.loss_key, self.loss_weight = loss_key, loss_weight
-        from . import configure_runtime
-        configure_runtime(warn=False)      # (normally too late here: the entry points call it first)
         self.static = {k: v.clone() for k, v in example_batch.items()}
         dev = model.arena().device
         if getattr(model, 'step_seed', None) is None or model.step_seed.device != dev:

@@ -16,6 +16,7 @@ as a scalar (`grad_scale`; sdmi.h: SdmiAdamArgs.gscale / g_dtype, SdmiSqSumArgs.
 format is an explicit argument (default fp32, like the reference's DDP); SDMI_GRAD_BF16=0 / 1 overrides.
 """
 import os
+import subprocess
 import sys
 
 import torch
@@ -23,10 +24,12 @@ import torch.distributed as dist
 
 
 def respawn_under_launcher(n_ranks, script, argv, port=None):
-    """Replace this process by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    script argv...` (one rank per GPU over RCCL; the reference's launch is
-    `torch.distributed.launch --nproc_per_node=$GPUS`, scripts/sbatch_run.sh:36-39).  Used by
-    `bench.py --gpus N` when it was started without a launcher.  Does not return."""
+    """Run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N script argv...` (one rank per
+    GPU over RCCL; the reference's launch is `torch.distributed.launch --nproc_per_node=$GPUS`,
+    scripts/sbatch_run.sh:36-39) as a fresh child process and exit with its status.  A child rather
+    than an exec of this process: the caller may already have started the HIP runtime (bench.py
+    counts the devices first).  Used by `bench.py --gpus N` when it was started without a launcher.
+    Does not return."""
     port = port or os.environ.get('MASTER_PORT', '29517')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={n_ranks}',
            '--master-addr', '127.0.0.1', '--master-port', str(port), script] + list(argv)
@@ -34,7 +37,8 @@ def respawn_under_launcher(n_ranks, script, argv, port=None):
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')      # dmabuf IPC (RCCL across processes)
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)        # (killed by a signal: the shell's 128 + signal number)
 
 
 def resolve_wire(wire=None):

@@ -88,3 +88,55 @@ def test_sampling_pass_b64_bf16_graph_against_fp32():
     assert R['eps_rel_l2'] < 0.02
     # measured on MI355X: eps rel-L2 0.99 %, final latents 0.10 %, VQ codes of the final latents 99.92 % equal
     assert R['latent_rel_l2'] < 0.02 and R['code_agreement'] > 0.99
+
+
+def _bench_run(out_dir, steps, warmup, *flags):
+    """One plain `bench.py` run (child process, B = 8) with --dump-outputs -> its result line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', str(steps), '--warmup', str(warmup),
+                        '--batch', '8', '--dump-outputs', str(out_dir)] + list(flags),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+
+
+def _dumped(d):
+    import numpy as np
+    arrays = {f[:-len('.npy')]: np.load(d / f) for f in sorted(p.name for p in d.iterdir())}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    return arrays
+
+
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """A plain bench.py run reports none of the --full legs; --steps sets the number of timed steps and --dump-outputs
+    writes the result of the last of them: 2 timed steps behind 1 warm-up step dump exactly what 1 timed step behind 2
+    warm-up steps dumps (the same three optimiser steps, bit-repeatable), 8 timed steps dump something else, and
+    ms_per_step stays the time of ONE step whether 1 or 8 are timed.  --mode sample dumps the final latents."""
+    import numpy as np
+    import bench
+    runs, outs = {}, {}
+    for tag, steps, warmup in (('s2w1', 2, 1), ('s1w2', 1, 2), ('s8w1', 8, 1)):
+        out = outs[tag] = _bench_run(tmp_path / tag, steps, warmup)
+        assert out['steps'] == steps and out['unit'] == 'images/s' and out['ms_per_step'] > 0 and out['finite']
+        assert out['denoise'] is None and out['comm'] is None and 'roofline' not in out and 'cpu_baseline' not in out
+        runs[tag] = _dumped(tmp_path / tag)
+        assert sorted(runs[tag]) == ['grads', 'loss', 'params']
+        assert float(runs[tag]['loss'][0]) == out['loss']
+    a = runs['s2w1']
+    assert a['params'].shape == a['grads'].shape == (bench.DUMP_SAMPLE,)
+    assert np.isfinite(a['grads']).all() and np.abs(a['grads']).max() > 0
+    for name in a:
+        assert np.array_equal(a[name], runs['s1w2'][name]), name
+    assert not np.array_equal(a['loss'], runs['s8w1']['loss'])
+    assert not np.array_equal(a['params'], runs['s8w1']['params'])
+    ratio = outs['s8w1']['ms_per_step'] / outs['s1w2']['ms_per_step']
+    assert 1 / 3 < ratio < 3, ratio          # (a count that ignored --steps would move it by 8x)
+    out = _bench_run(tmp_path / 'sample', 2, 1, '--mode', 'sample')
+    assert out['steps'] == 2 and out['unit'] == 'image-denoise-steps/s' and out['ms_per_step'] > 0 and out['finite']
+    lat = _dumped(tmp_path / 'sample')
+    assert sorted(lat) == ['latents'] and lat['latents'].shape == (8, 3, 32, 32) and np.isfinite(lat['latents']).all()

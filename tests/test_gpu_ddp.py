@@ -103,7 +103,7 @@ def test_bench_rccl_path_single_rank():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SDMI_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--only-train', '--no-cpu-baseline',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--only-train', '--no-cpu-baseline',
                         '--no-roofline', '--steps', '2', '--warmup', '1', '--batch', '8'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -102,7 +102,7 @@ def test_bucket_bounds_cover_everything():
 
 
 def test_respawn_under_launcher_starts_n_ranks(tmp_path):
-    """bench.py --gpus N without a launcher re-executes itself under torch.distributed.run
+    """bench.py --gpus N without a launcher runs itself again in a child torch.distributed.run
     (parallel.respawn_under_launcher): N ranks, each with RANK / WORLD_SIZE / MASTER_ADDR set and a
     working process group (gloo here, RCCL on the GPU box)."""
     import subprocess

@@ -13,8 +13,9 @@ rows.sort()
 adam = [i for i, r in enumerate(rows) if 'adam_kernel' in r[2]]
 # a step = (previous step's last adam, this step's last adam]
 ends = [adam[i] for i in range(len(adam)) if i + 1 == len(adam) or adam[i + 1] != adam[i] + 1]
-# (bench.py runs one more step behind its closing barrier: that one starts on an idle queue, ~0.4 ms of host launch
-# latency in front of its first kernel -- take the last step of the timed loop instead)
+# (bench.py --full runs one more step behind its closing barrier: that one starts on an idle queue, ~0.4 ms of host
+# launch latency in front of its first kernel -- take the step before the last instead: the last step of the timed
+# loop there, its next-to-last step in a plain run)
 k = -2 if len(ends) >= 3 else -1
 seg = rows[ends[k - 1] + 1:ends[k] + 1]
 span = seg[-1][1] - seg[0][0]
