@@ -399,6 +399,39 @@ typedef struct {
 int sdmi_vq_nearest(const SdmiVqArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The tail of ONE function evaluation of the DPM-Solver++ family in one launch (ddpm/dpm_solver.py):
+ *   data prediction from the evaluated state x and the network output `out`, per prediction target
+ *     SDMI_DPM_EPS  x0 = (x - sigma * out) / alpha                                   data_prediction_fn 523-534
+ *     SDMI_DPM_X0   eps = (x - alpha * out) / sigma, then as EPS                     model_wrapper 358-361
+ *     SDMI_DPM_V    eps = alpha * out + sigma * x,   then as EPS                     model_wrapper 362-365
+ *   -> VQ nearest code (sdmi_vq_nearest's codes-in-registers search: the same indices, non-finite rows included;
+ *      vqvae/quantize.py:85-94) -> m0 (the quantised prediction, kept as solver history; idx optional)
+ *   -> the solver update y from a base state (for singlestep inner evaluations not the evaluated state), m0 and up to
+ *      two earlier predictions h1 (previous) and h2 (the one before):
+ *     SDMI_DPM_UPD_NONE    no update (denoise_to_zero_fn 633-637: m0 is the result)
+ *     SDMI_DPM_UPD_FIRST   y = c0*base + c1*m0                                       dpm_solver_first_update 665-668
+ *     SDMI_DPM_UPD_SINGLE  y = (c0*base + c1*h1) + c2*(m0 - h1)                      singlestep 2nd / 3rd, 728-732, 820-831
+ *     SDMI_DPM_UPD_MULTI2  D1_0 = k0*(m0 - h1);  y = (c0*base + c1*m0) + c2*D1_0     multistep 2nd, 912-923
+ *     SDMI_DPM_UPD_MULTI3  D1_0 as above, D1_1 = k1*(h1 - h2), D1 = D1_0 + g*(D1_0 - D1_1), D2 = k2*(D1_0 - D1_1);
+ *                          y = ((c0*base + c1*m0) + c2*D1) + c3*D2                   multistep 3rd, 968-985
+ * Every expression is evaluated op by op in this order without FMA contraction: the bits are those of the chain of
+ * sdmi_vq_nearest + sdmi_lincomb launches that spells it.  x, base, h1, h2, m0, y are [R][4] fp32 rows (16-byte
+ * aligned; pad channel read as stored, written 0); only the first 3 channels of `out` [R][4] are read.
+ * ------------------------------------------------------------------------------------------ */
+enum { SDMI_DPM_EPS = 0, SDMI_DPM_X0 = 1, SDMI_DPM_V = 2 };
+enum { SDMI_DPM_UPD_NONE = 0, SDMI_DPM_UPD_FIRST = 1, SDMI_DPM_UPD_SINGLE = 2, SDMI_DPM_UPD_MULTI2 = 3,
+       SDMI_DPM_UPD_MULTI3 = 4 };
+typedef struct {
+  const float* x; const float* out; const float* codebook;
+  long long* idx; float* m0;
+  const float* base; const float* h1; const float* h2; float* y;
+  int R, n_codes, target, mode;
+  float scale, sigma, alpha;
+  float c0, c1, c2, c3, k0, k1, g, k2;
+} SdmiDpmStepArgs;
+int sdmi_dpm_step(const SdmiDpmStepArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Small fused elementwise kernels.
  * ------------------------------------------------------------------------------------------ */
 /* y = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div   (fp32; NULL operands skipped, x3 NULL -> c2*x2,

@@ -53,11 +53,12 @@ __device__ __forceinline__ float vq_dist1(float z0, float z1, float z2, float zz
 // Non-finite latents (NaN / Inf components, or |z|^2 overflowing): the packed scan's fminf drops NaN distances, so no
 // code "attains the minimum" and the index would stay at its sentinel.  These rows take a sequential scan with
 // torch.argmin's semantics (vqvae/quantize.py:90): the first NaN distance if there is one, else the first minimum.
-__device__ __noinline__ int vq_scan_nonfinite(const SdmiVqArgs& p, float z0, float z1, float z2, float zz) {
+__device__ __noinline__ int vq_scan_nonfinite(const float* __restrict__ codebook, int n_codes, float z0, float z1, float z2,
+                                              float zz) {
   float best = INFINITY;
   int bi = 0;
-  for (int j = 0; j < p.n_codes; ++j) {
-    const float a = p.codebook[j * 3 + 0], b = p.codebook[j * 3 + 1], c = p.codebook[j * 3 + 2];
+  for (int j = 0; j < n_codes; ++j) {
+    const float a = codebook[j * 3 + 0], b = codebook[j * 3 + 1], c = codebook[j * 3 + 2];
     const float t0 = a * a, t1 = b * b, t2 = c * c;
     // (the reference's separately rounded 2 * dot: equal to the scan's fma(-2, dot, .) except where 2 * dot overflows,
     // which only these rows can reach -- inf - inf = NaN there, +-inf from the fused form)
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void vq_kernel(SdmiVqArgs p) {
     if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
   if (!live || half) return;
-  if (!(zz < INFINITY)) bi = vq_scan_nonfinite(p, z0, z1, z2, zz);
+  if (!(zz < INFINITY)) bi = vq_scan_nonfinite(p.codebook, p.n_codes, z0, z1, z2, zz);
   if (p.idx) p.idx[r] = bi;
   if (p.zq) {
     float* o = p.zq + (long long)r * p.ldz;
@@ -169,13 +170,16 @@ __device__ __forceinline__ float vq_wave_min(float v) {
 }
 
 
+// The search shared by vq_reg_kernel and dpm_step_kernel: every thread of the 256-thread workgroup calls it with the
+// (scaled) latent of row r0 + lane; `owner` (tid < VQ_LAT and a live row) gets the row's code index back, non-finite
+// rows included.  One body, so the two kernels cannot disagree on an index.
 template <int NP>
-__global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
+__device__ __forceinline__ int vq_reg_search(const float* __restrict__ codebook, int n_codes, float z0, float z1, float z2,
+                                             float zz, bool owner) {
   __shared__ float res_d[4][VQ_LAT];
   __shared__ unsigned long long res_b[4][VQ_LAT];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r0 = blockIdx.x * VQ_LAT;
   const int cbase = w * 128 * NP;
   vq_f2 e0[NP], e1[NP], e2[NP], e3[NP];
 #pragma unroll
@@ -184,21 +188,14 @@ __global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
     for (int k = 0; k < 2; ++k) {
       const int j = cbase + q * 128 + lane * 2 + k;
       float a = 0.f, b = 0.f, c = 0.f, n2 = INFINITY;              // pad codes: distance +inf
-      if (j < p.n_codes) {
-        a = p.codebook[j * 3 + 0]; b = p.codebook[j * 3 + 1]; c = p.codebook[j * 3 + 2];
+      if (j < n_codes) {
+        a = codebook[j * 3 + 0]; b = codebook[j * 3 + 1]; c = codebook[j * 3 + 2];
         const float s0 = a * a, s1 = b * b, s2 = c * c;
         n2 = (s0 + s1) + s2;
       }
       e0[q][k] = a; e1[q][k] = b; e2[q][k] = c; e3[q][k] = n2;
     }
   }
-  // every wave holds the workgroup's latents, one per lane
-  const int r = r0 + lane;
-  const float* zr = p.z + (long long)(r < p.R ? r : 0) * p.ldz;
-  const float* z2r = p.z2 ? p.z2 + (long long)(r < p.R ? r : 0) * p.ldz : nullptr;
-  const float z0 = vq_chan(p, zr, z2r, 0), z1 = vq_chan(p, zr, z2r, 1), z2 = vq_chan(p, zr, z2r, 2);
-  const float zq0 = z0 * z0, zq1 = z1 * z1, zq2 = z2 * z2;
-  const float zz = (zq0 + zq1) + zq2;
   float keep_d = INFINITY;
   unsigned keep_lo = 0, keep_hi = 0;
   const vq_f2 m2 = {-2.f, -2.f};
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
   res_d[w][lane] = keep_d;
   res_b[w][lane] = ((unsigned long long)keep_hi << 32) | keep_lo;
   __syncthreads();
-  if (tid >= VQ_LAT || r >= p.R) return;
+  if (!owner) return 0;
   int wb = 0;
   float best = res_d[0][tid];
 #pragma unroll
@@ -241,15 +238,31 @@ __global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
     for (int q = 0; q < NP; ++q) {
       for (int k = 0; k < 2; ++k) {
         const int j = wb * 128 * NP + q * 128 + L * 2 + k;
-        if (j < p.n_codes && j < bi) {
-          const float a = p.codebook[j * 3 + 0], b = p.codebook[j * 3 + 1], c = p.codebook[j * 3 + 2];
+        if (j < n_codes && j < bi) {
+          const float a = codebook[j * 3 + 0], b = codebook[j * 3 + 1], c = codebook[j * 3 + 2];
           const float t0 = a * a, t1 = b * b, t2 = c * c;
           if (vq_dist1(z0, z1, z2, zz, a, b, c, (t0 + t1) + t2) == best) bi = j;
         }
       }
     }
   }
-  if (!(zz < INFINITY)) bi = vq_scan_nonfinite(p, z0, z1, z2, zz);
+  if (!(zz < INFINITY)) bi = vq_scan_nonfinite(codebook, n_codes, z0, z1, z2, zz);
+  return bi;
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  // every wave holds the workgroup's latents, one per lane
+  const int r = blockIdx.x * VQ_LAT + lane;
+  const float* zr = p.z + (long long)(r < p.R ? r : 0) * p.ldz;
+  const float* z2r = p.z2 ? p.z2 + (long long)(r < p.R ? r : 0) * p.ldz : nullptr;
+  const float z0 = vq_chan(p, zr, z2r, 0), z1 = vq_chan(p, zr, z2r, 1), z2 = vq_chan(p, zr, z2r, 2);
+  const float zq0 = z0 * z0, zq1 = z1 * z1, zq2 = z2 * z2;
+  const float zz = (zq0 + zq1) + zq2;
+  const bool owner = tid < VQ_LAT && r < p.R;
+  const int bi = vq_reg_search<NP>(p.codebook, p.n_codes, z0, z1, z2, zz, owner);
+  if (!owner) return;
   if (p.idx) p.idx[r] = bi;
   if (p.zq) {
     float* o = p.zq + (long long)r * p.ldz;
@@ -258,6 +271,83 @@ __global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
     o[0] = c0_ / p.scale; o[1] = c1_ / p.scale; o[2] = c2_ / p.scale;
     for (int c = 3; c < p.ldz; ++c) o[c] = 0.f;
   }
+}
+
+// ---- one function evaluation's tail of the DPM-Solver++ family (include/sdmi.h: sdmi_dpm_step) -------------------------
+// Lane t of the workgroup owns row r0 + t from the load to the last store: it forms the data prediction from the evaluated
+// state and the network output (sdmi_lincomb's operations in sdmi_lincomb's order, per target), runs through the shared
+// search, and -- as the row's owner -- writes the quantised prediction m0 and the solver update, each as ONE 16-byte
+// vector store.  Every expression below is spelled op by op like the chain of sdmi_lincomb launches it replaces (this file
+// is compiled with -ffp-contract=off), so the bits are the chain's.
+__device__ __forceinline__ float dpm_x0(const SdmiDpmStepArgs& p, float x, float o) {
+  float eps = o;                                         // SDMI_DPM_EPS: the network predicts the noise
+  if (p.target == SDMI_DPM_X0) {                         // model_wrapper 358-361: (x - alpha * out) / sigma
+    const float t0 = 1.0f * x, t1 = (-p.alpha) * o;
+    eps = (t0 + t1) / p.sigma;
+  } else if (p.target == SDMI_DPM_V) {                   // 362-365: alpha * out + sigma * x
+    const float t0 = p.alpha * o, t1 = p.sigma * x;
+    eps = t0 + t1;
+  }
+  const float t0 = 1.0f * x, t1 = (-p.sigma) * eps;      // data_prediction_fn 529: (x - sigma * eps) / alpha
+  return (t0 + t1) / p.alpha;
+}
+
+__device__ __forceinline__ float dpm_update(const SdmiDpmStepArgs& p, float x, float m0, float h1, float h2) {
+  if (p.mode == SDMI_DPM_UPD_FIRST) {                    // c0 * x + c1 * m0
+    const float t0 = p.c0 * x, t1 = p.c1 * m0;
+    return t0 + t1;
+  }
+  if (p.mode == SDMI_DPM_UPD_SINGLE) {                   // (c0 * x + c1 * h1) + c2 * (m0 - h1)
+    const float t0 = p.c0 * x, t1 = p.c1 * h1;
+    const float d = m0 - h1, t2 = p.c2 * d;
+    return (t0 + t1) + t2;
+  }
+  const float d0 = m0 - h1;
+  const float D1_0 = p.k0 * d0;                          // D1_0 = (1 / r0) * (m0 - h1)
+  const float t0 = p.c0 * x, t1 = p.c1 * m0;
+  if (p.mode == SDMI_DPM_UPD_MULTI2) {                   // (c0 * x + c1 * m0) + c2 * D1_0
+    const float t2 = p.c2 * D1_0;
+    return (t0 + t1) + t2;
+  }
+  const float d1 = h1 - h2;
+  const float D1_1 = p.k1 * d1;                          // D1_1 = (1 / r1) * (h1 - h2)
+  const float dd = D1_0 - D1_1;
+  const float gd = p.g * dd;
+  const float D1 = 1.0f * D1_0 + gd;                     // D1 = D1_0 + r0 / (r0 + r1) * (D1_0 - D1_1)
+  const float D2 = p.k2 * dd;                            // D2 = 1 / (r0 + r1) * (D1_0 - D1_1)
+  const float t2 = p.c2 * D1, t3 = p.c3 * D2;
+  const float y1 = (t0 + t1) + t2;
+  const float u0 = 1.0f * y1;
+  return u0 + t3;                                        // ((c0 * x + c1 * m0) + c2 * D1) + c3 * D2
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void dpm_step_kernel(SdmiDpmStepArgs p) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = blockIdx.x * VQ_LAT + lane;
+  const long long ro = (long long)(r < p.R ? r : 0) * 4;
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + ro);
+  const float* o = p.out + ro;                           // (the pad channel of the network output is never read)
+  const float p0 = dpm_x0(p, xv[0], o[0]), p1 = dpm_x0(p, xv[1], o[1]), p2 = dpm_x0(p, xv[2], o[2]);
+  const float z0 = p0 * p.scale, z1 = p1 * p.scale, z2 = p2 * p.scale;
+  const float zq0 = z0 * z0, zq1 = z1 * z1, zq2 = z2 * z2;
+  const float zz = (zq0 + zq1) + zq2;
+  const bool owner = tid < VQ_LAT && r < p.R;
+  const int bi = vq_reg_search<NP>(p.codebook, p.n_codes, z0, z1, z2, zz, owner);
+  if (!owner) return;
+  if (p.idx) p.idx[r] = bi;
+  const float c0_ = z0 + (p.codebook[bi * 3 + 0] - z0), c1_ = z1 + (p.codebook[bi * 3 + 1] - z1),
+              c2_ = z2 + (p.codebook[bi * 3 + 2] - z2);
+  const f32x4 m = {c0_ / p.scale, c1_ / p.scale, c2_ / p.scale, 0.f};
+  *reinterpret_cast<f32x4*>(p.m0 + ro) = m;
+  if (p.mode == SDMI_DPM_UPD_NONE) return;
+  const f32x4 bv = *reinterpret_cast<const f32x4*>(p.base + ro);
+  f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
+  if (p.mode >= SDMI_DPM_UPD_SINGLE) h1 = *reinterpret_cast<const f32x4*>(p.h1 + ro);
+  if (p.mode == SDMI_DPM_UPD_MULTI3) h2 = *reinterpret_cast<const f32x4*>(p.h2 + ro);
+  const f32x4 y = {dpm_update(p, bv[0], m[0], h1[0], h2[0]), dpm_update(p, bv[1], m[1], h1[1], h2[1]),
+                   dpm_update(p, bv[2], m[2], h1[2], h2[2]), 0.f};
+  *reinterpret_cast<f32x4*>(p.y + ro) = y;
 }
 
 }  // namespace
@@ -278,4 +368,20 @@ extern "C" int sdmi_vq_nearest(const SdmiVqArgs* a, void* stream) {
   SDMI_OPTIN_LDS(vq_kernel, 160 * 1024, "vq_nearest");
   hipLaunchKernelGGL(vq_kernel, dim3((a->R + 127) / 128), dim3(256), smem, (hipStream_t)stream, *a);
   return sdmi_check_launch("vq_nearest");
+}
+
+extern "C" int sdmi_dpm_step(const SdmiDpmStepArgs* a, void* stream) {
+  SDMI_REQUIRE(a && a->x && a->out && a->codebook && a->m0, "null pointer");
+  SDMI_REQUIRE(a->R >= 1 && a->n_codes >= 1 && a->n_codes <= 4 * 128 * 16, "bad shape (codebooks up to 8192 codes)");
+  SDMI_REQUIRE(a->target >= SDMI_DPM_EPS && a->target <= SDMI_DPM_V, "unknown prediction target");
+  SDMI_REQUIRE(a->mode >= SDMI_DPM_UPD_NONE && a->mode <= SDMI_DPM_UPD_MULTI3, "unknown update form");
+  SDMI_REQUIRE(a->mode == SDMI_DPM_UPD_NONE || (a->base && a->y), "update without base / destination");
+  SDMI_REQUIRE(a->mode < SDMI_DPM_UPD_SINGLE || a->h1, "update form needs the previous prediction");
+  SDMI_REQUIRE(a->mode != SDMI_DPM_UPD_MULTI3 || a->h2, "third-order update needs two previous predictions");
+  SDMI_REQUIRE(a->scale != 0.f && a->alpha != 0.f && (a->target != SDMI_DPM_X0 || a->sigma != 0.f), "zero divisor");
+  const dim3 grid((a->R + VQ_LAT - 1) / VQ_LAT);
+  if (a->n_codes <= 4 * 128 * 4) hipLaunchKernelGGL(dpm_step_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  else if (a->n_codes <= 4 * 128 * 8) hipLaunchKernelGGL(dpm_step_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(dpm_step_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  return sdmi_check_launch("dpm_step");
 }

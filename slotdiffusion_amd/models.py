@@ -215,10 +215,27 @@ class LDM(_Owned):
     # -- a12/a13 -------------------------------------------------------------------------
     @torch.no_grad()
     def generate_imgs(self, cond, batch_size=16, ret_intermed=False, verbose=False,
-                      use_ddim=False, use_dpm=True, x_T=None, same_noise=False, **kwargs):
+                      use_ddim=False, use_dpm=True, x_T=None, same_noise=False, dpm_steps=None, dpm_order=3,
+                      dpm_method='singlestep', dpm_skip_type='time_uniform', dpm_t_start=None, dpm_t_end=None,
+                      dpm_denoise_to_zero=False, dpm_lower_order_final=True, **kwargs):
         """cond_ddpm.py:134-212: DPM-Solver++ (use_dpm, takes precedence), DDIM (use_ddim) or the
-        T-step ancestral sampler.  Returns latents [B,3,h,w] (NCHW fp32)."""
+        T-step ancestral sampler.  Returns latents [B,3,h,w] (NCHW fp32).
+
+        The dpm_* keywords are DPM_Solver.sample's (dpm_solver.py:1190-1345): steps (None: max(20, T // 50) as the
+        reference's caller passes), order 1-3, method 'singlestep' | 'singlestep_fixed' | 'multistep', skip_type
+        'time_uniform' | 'logSNR' | 'time_quadratic', t_start / t_end (x_T is then the state AT t_start: see
+        noise_latent), denoise_to_zero, lower_order_final.  Not built, and refused with a ValueError naming the
+        argument: dpm_method='adaptive', dpm_solver_type='taylor', dpm_algorithm_type='dpmsolver',
+        dpm_correcting_x0_fn (dynamic thresholding), guidance_scale != 1.  With ret_intermed the second result is the
+        reference's `intermediates`: one state per outer step (singlestep), the initial state and one per step
+        (multistep), then the denoise_to_zero state when asked."""
         r = self.root
+        if use_dpm:
+            dpm.check_options(method=dpm_method, order=dpm_order, skip_type=dpm_skip_type,
+                              solver_type=kwargs.get('dpm_solver_type', 'dpmsolver'),
+                              algorithm_type=kwargs.get('dpm_algorithm_type', 'dpmsolver++'),
+                              correcting_x0_fn=kwargs.get('dpm_correcting_x0_fn'),
+                              guidance_scale=kwargs.get('guidance_scale', 1.))
         if cond.dim() == 2:
             cond = cond.unsqueeze(0).expand(batch_size, -1, -1)
         cond = cond.contiguous()
@@ -230,7 +247,9 @@ class LDM(_Owned):
                 x_T = torch.randn(batch_size, 3, h, w, device=cond.device)
         x = ops.nchw_to_nhwc(x_T, torch.float32, 4)
         if use_dpm:            # cond_ddpm.py:155-178 (takes precedence, as in the reference)
-            x, inter = r._dpm_sample(x, cond, ret_intermed)
+            x, inter = r._dpm_sample(x, cond, ret_intermed, steps=dpm_steps, order=dpm_order, method=dpm_method,
+                                     skip_type=dpm_skip_type, t_start=dpm_t_start, t_end=dpm_t_end,
+                                     denoise_to_zero=dpm_denoise_to_zero, lower_order_final=dpm_lower_order_final)
         elif use_ddim:         # cond_ddpm.py:180-190: DDIM, max(200, T // 5) steps, eta = 0
             steps = kwargs.get('ddim_steps') or max(200, self.num_timesteps // 5)
             x, inter = r._ddim_sample(x, cond, steps, kwargs.get('eta', 0.), ret_intermed,
@@ -241,6 +260,17 @@ class LDM(_Owned):
         if ret_intermed:
             return out, torch.stack([ops.nhwc_to_nchw(i, 3) for i in inter], 0)
         return out
+
+    @torch.no_grad()
+    def noise_latent(self, z0, t, noise=None):
+        """alpha(t) * z0 + sigma(t) * noise at a CONTINUOUS time t in [1 / T, 1] on the solver's schedule
+        (dpm.DiscreteSchedule: NoiseScheduleVP.marginal_alpha / marginal_std, dpm_solver.py:199-209), one sdmi_lincomb
+        launch: the state generate_imgs(x_T=..., dpm_t_start=t) starts from.  z0, noise: latents [B,3,h,w]."""
+        ns = dpm.DiscreteSchedule(self.betas.detach().float().cpu())
+        tt = torch.tensor([float(t)])
+        z0 = z0.float().contiguous()
+        noise = torch.randn_like(z0) if noise is None else noise.float().contiguous()
+        return ops.lincomb(float(ns.alpha(tt)), z0, float(ns.std(tt)), noise)
 
     @torch.no_grad()
     def log_images(self, batch, ret_intermed=False, **kwargs):
@@ -374,7 +404,7 @@ class SADiffusion(SlotModelBase):
         self.dm_decoder.vae._bind(self)
         self._bank = None
         self._unet = None
-        self._plan = None
+        self._plans = {}           # solver configuration (dpm.plan_key) -> (plan, model times on the device, program)
         self._Kinf = self._Kgrad = None
         self.step_seed = None      # device word mixed into dropout seeds (see optim.GraphedTrainStep)
         self.eval_seed = None      # its no_grad / validation counterpart (LDM._draw_tn)
@@ -408,27 +438,33 @@ class SADiffusion(SlotModelBase):
                          u.context_kv(Kp, self._ctx(slots, Kp)))
 
     # -- sampler -------------------------------------------------------------------------
-    def _dpm_sample(self, x, cond, ret_intermed=False, steps=None):
-        """x [B,h,w,4] fp32 noise -> x_0.  With use_graph the whole 20-NFE loop (~9k kernel
-        launches) is captured once per batch size into a HIP graph and replayed."""
+    def _dpm_sample(self, x, cond, ret_intermed=False, steps=None, **solver):
+        """x [B,h,w,4] fp32 noise -> x_0.  With use_graph the whole loop (~9k kernel launches at 20 NFE) is captured once
+        per batch size, condition shape and solver configuration into a HIP graph and replayed.  `solver`: the keywords
+        of dpm.build_plan; the default (singlestep, order 3, uniform grid) runs _dpm_loop, every other configuration
+        _dpm_family_loop."""
         steps = steps or max(20, self.dm_decoder.num_timesteps // 50)
+        cfg = dpm.plan_key(steps, **solver)
+        dflt = dpm.plan_key(steps)
+        default = cfg[:6] + cfg[7:] == dflt[:6] + dflt[7:]          # (lower_order_final means nothing to singlestep)
+        loop = self._dpm_loop if default else self._dpm_family_loop
         if ret_intermed or not self.use_graph:
-            return self._dpm_loop(x, cond, self._dpm_prepare(steps, x.device), ret_intermed)
-        key = (x.shape[0], steps, tuple(cond.shape))
+            return loop(x, cond, self._dpm_prepare(cfg, x.device), ret_intermed)
+        key = (x.shape[0], cfg, tuple(cond.shape))
         g = self._graph_cache.get(key)
         if g is None:
-            prep = self._dpm_prepare(steps, x.device)
+            prep = self._dpm_prepare(cfg, x.device)
             sx, sc = torch.empty_like(x), torch.empty_like(cond)
             sx.copy_(x)
             sc.copy_(cond)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):            # warm-up: lazy weight prep, func attributes
-                self._dpm_loop(sx, sc, prep, False)
+                loop(sx, sc, prep, False)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                out, _ = self._dpm_loop(sx, sc, prep, False)
+                out, _ = loop(sx, sc, prep, False)
             g = self._graph_cache[key] = (graph, sx, sc, out)
         graph, sx, sc, out = g
         sx.copy_(x)
@@ -519,16 +555,48 @@ class SADiffusion(SlotModelBase):
                 x = ops.lincomb(1.0, x, st['sigma'], nz)
             yield x, st
 
-    def _dpm_prepare(self, steps, device):
-        if self._plan is None or self._plan[0] != steps:
+    @staticmethod
+    def dpm_cache_key(batch, cond_shape, steps=20, **solver):
+        """Key of the HIP-graph cache entry of one sampler call: batch, the full solver configuration, condition shape."""
+        return (batch, dpm.plan_key(steps, **solver), tuple(cond_shape))
+
+    def _dpm_prepare(self, cfg, device):
+        """cfg (dpm.plan_key) -> (plan, model times of its evaluations on the device, flat program); one entry per
+        configuration and device, so alternating configurations rebuild nothing."""
+        ent = self._plans.get((cfg, device))
+        if ent is None:
             betas = self.dm_decoder.betas.detach().float().cpu()
-            plan = dpm.build_plan(betas, steps=steps, order=3)
+            names = ('steps', 'order', 'method', 'skip_type', 't_start', 't_end', 'lower_order_final', 'denoise_to_zero')
+            plan = dpm.build_plan(betas, **dict(zip(names, cfg)))
             tin = torch.tensor(dpm.plan_t_inputs(plan), dtype=torch.float32, device=device)
-            self._plan = (steps, plan, tin)
-        return self._plan[1], self._plan[2]
+            ent = self._plans[(cfg, device)] = (plan, tin, dpm.program(plan))
+        return ent
+
+    def _dpm_family_loop(self, x, cond, prep, ret_intermed):
+        """Every solver configuration but the default: per function evaluation the UNet and ONE sdmi_dpm_step launch
+        (data prediction for the model's target, VQ, solver update), driven by dpm.run_program."""
+        plan, tin, prog = prep
+        u = self.unet()
+        Kp = self.K()
+        ctx_kv = u.context_kv(Kp, self._ctx(cond))
+        rv_all = u.time_rowvecs(Kp, tin)
+        B = x.shape[0]
+        code = self.bank().f(self.vq_key)
+        target = self.dm_decoder.pred_target
+        nfe = [0]
+
+        def tail(xc, e, upd, base, h1, h2):
+            rv = rv_all[nfe[0]:nfe[0] + 1].expand(B, -1)
+            nfe[0] += 1
+            out = u.forward(Kp, self._unet_in(xc), rv, ctx_kv, zero_pad=False)     # (the pad channel is never read)
+            m0, y, _ = ops.dpm_step(xc, out, code, e, scale=self.z_scale, target=target, upd=upd, base=base, h1=h1, h2=h2)
+            return m0, y
+
+        x, inter = dpm.run_program(prog, x, tail, emit_initial=plan.get('method') == 'multistep')
+        return x, (inter if ret_intermed else [])
 
     def _dpm_loop(self, x, cond, prep, ret_intermed):
-        plan, tin = prep
+        plan, tin = prep[:2]
         u = self.unet()
         Kp = self.K()
         ctx_kv = u.context_kv(Kp, self._ctx(cond))

@@ -478,6 +478,32 @@ def vq_nearest(z, codebook, *, scale=1.0, want_idx=True, want_zq=True, comb=None
     return idx, zq
 
 
+_DPM_TARGET = {'eps': 0, 'x0': 1, 'v': 2}     # sdmi.h: SDMI_DPM_EPS / _X0 / _V
+
+
+def dpm_step(x, out, codebook, e, *, scale=1.0, target='eps', upd=None, base=None, h1=None, h2=None, want_idx=False):
+    """One function evaluation's tail in one launch (sdmi.h: sdmi_dpm_step): data prediction of state x [..., 4] from the
+    network output `out` at the evaluation record e (sigma, alpha), nearest code, and -- with upd (a dpm.program update:
+    mode + coefficients) -- the solver update from `base`, the prediction and the earlier predictions h1, h2.
+    -> (m0, y or None, idx or None)."""
+    _need_gpu(x, out, codebook)
+    assert x.shape[-1] == 4 and out.shape == x.shape and codebook.shape[1] == 3
+    ts = [t for t in (x, out, base, h1, h2) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape for t in ts)
+    R = x.numel() // 4
+    m0 = torch.empty_like(x)
+    idx = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device) if want_idx else None
+    kw, y = {}, None
+    if upd is not None:
+        y = torch.empty_like(x)
+        kw = dict(mode=upd['mode'], base=_p(base), h1=_p(h1), h2=_p(h2), y=_p(y),
+                  **{k: float(upd[k]) for k in ('c0', 'c1', 'c2', 'c3', 'k0', 'k1', 'g', 'k2') if k in upd})
+    call('sdmi_dpm_step', _stream(), x=_p(x), out=_p(out), codebook=_p(codebook), idx=_p(idx), m0=_p(m0), R=R,
+         n_codes=codebook.shape[0], target=_DPM_TARGET[target], scale=scale, sigma=float(e['sigma']),
+         alpha=float(e['alpha']), **kw)
+    return m0, y, idx
+
+
 def lincomb(c0=0., x0=None, c1=0., x1=None, c2=0., x2=None, x3=None, div=0., out=None):
     """out = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div  (fp32 tensors; see sdmi.h)."""
     ref = x0 if x0 is not None else (x1 if x1 is not None else x2)

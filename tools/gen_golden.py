@@ -344,6 +344,202 @@ def main_vpred():
     print('wrote vpred_b1t2.npz', {k: tuple(np.asarray(v).shape) for k, v in arrs.items()})
 
 
+# ---- DPM-Solver++ family (tests/golden/dpm_family_b2.npz) ---------------------------------------------------------
+DPM_FAMILY = [          # (tag, DPM_Solver.sample keyword arguments)
+    ('ms2_10', dict(method='multistep', order=2, steps=10)),
+    ('ms3_15_logsnr', dict(method='multistep', order=3, steps=15, skip_type='logSNR')),
+    ('ms3_8_lof', dict(method='multistep', order=3, steps=8)),                 # lower_order_final taken (steps < 10)
+    ('ss2_10_quad_d0', dict(method='singlestep', order=2, steps=10, skip_type='time_quadratic', denoise_to_zero=True)),
+    ('ss3_12_t06', dict(method='singlestep', order=3, steps=12, t_start=0.6)),
+]
+DPM_GAP_MIN = 1e-4       # smallest allowed (second-nearest - nearest) code distance over every quantisation
+# Configurations for which NO draw met DPM_GAP_MIN: started from the encoder's own x0 the predictions sit where the codes
+# are dense, about 40 % of the evaluations have a gap under 1e-4 and none of ~2400 draws (seeds 7 .. 2400) got through all
+# 12.  Such a configuration is generated from the first seed with its gap RECORDED and `guard_met` = 0 in the file.
+DPM_GUARD_UNMET = ('ss3_12_t06',)
+TOY_STEP, TOY_CLAMP = 0.5, 1.5
+TOY_GAP_MIN = 1e-4      # smallest allowed distance of a toy data prediction from a rounding boundary
+
+
+def toy_params(seed=31):
+    """Parameters of the toy noise model (stored in the fixture): per-element gain / bias / time slope [3,8,8]."""
+    g = torch.Generator().manual_seed(seed)
+    return dict(toy_A=0.9 + 0.1 * torch.rand(3, 8, 8, generator=g), toy_C=0.05 * torch.randn(3, 8, 8, generator=g),
+                toy_D=0.1 * torch.randn(3, 8, 8, generator=g))
+
+
+def toy_eps(P, x, t_input):
+    """eps(x, t) = A * x + C + D * (t_input / 1000): elementwise only, so every CPU evaluates the same bits; A just under
+    1 keeps the data prediction (x - sigma eps) / alpha O(1) where alpha is small."""
+    return P['toy_A'] * x + P['toy_C'] + P['toy_D'] * (t_input.reshape(-1, 1, 1, 1) / 1000.)
+
+
+def toy_quantize(x0):
+    """The toy quantiser: round to a grid of pitch TOY_STEP, clamped to +-TOY_CLAMP."""
+    return torch.clamp(torch.round(x0 / TOY_STEP) * TOY_STEP, -TOY_CLAMP, TOY_CLAMP)
+
+
+def toy_gap(x0):
+    """Smallest distance of x0 from a rounding boundary (k + 0.5) * TOY_STEP, over the elements the clamp does not decide."""
+    u = x0 / TOY_STEP
+    inside = u.abs() < TOY_CLAMP / TOY_STEP
+    d = (u - torch.floor(u) - 0.5).abs() * TOY_STEP
+    return float(torch.where(inside, d, torch.ones_like(d)).min())
+
+
+def write_npz_fixed(path, arrs):
+    """np.savez_compressed with constant zip timestamps, so that the same arrays give the same file bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as zf:
+        for k in arrs:
+            zi = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(zi, 'w', force_zip64=True) as fh:
+                np.lib.format.write_array(fh, np.asanyarray(arrs[k]), allow_pickle=False)
+
+
+def _stored_states(n):
+    """Indices of the intermediates kept: the first, one from the warm-up, mid-trajectory, the last but one, the last."""
+    return sorted({0, 1, n // 2, n - 2, n - 1})
+
+
+class _NearTie(Exception):
+    pass
+
+
+def main_dpm_family():
+    """tests/golden/dpm_family_b2.npz: the reference's DPM_Solver (model_wrapper + DPM_Solver(algorithm_type=
+    'dpmsolver++', correcting_x0_fn=False, vq_denoised=True), dpm_solver.py:1190-1345) for the DPM_FAMILY configurations
+    (a) on the model, slots and x_T of sadiff_b2.npz, (b) on a toy model (toy_eps / toy_quantize) with 2x3x8x8 states.
+    Every quantisation of every trajectory is checked for near-ties (DPM_GAP_MIN): a configuration that has one is
+    redrawn from the next x_T seed, which the file records."""
+    import json
+    from oracle import slotdiff_oracle as O
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    im = rh.ref_models('img_based')
+    P = rh.ref_params('img_based', 'sa_ldm', 'sa_ldm_clevrtex_params-res128')
+    P.slot_dict['num_slots'] = 7
+    model = im.build_model(P)
+    det_fill_(model.state_dict().items(), skip=is_buffer_name)
+    model.eval()
+    img, t, noise, x_T0 = make_inputs(2)
+    with torch.no_grad():
+        slots, _ = model.encode(img)
+        dm = model.dm_decoder
+        x0 = dm.vae.encode(img)
+    from slotdiffusion.img_based.models.ddpm import dpm_solver as ds
+    ns = ds.NoiseScheduleVP(betas=dm.betas)
+    gaps = []
+
+    def watch(mod, args):            # every latent the VQ sees: gap between its two nearest code distances
+        z = args[0].permute(0, 2, 3, 1).reshape(-1, 3)
+        e = mod.embedding.weight
+        d = torch.sum(z ** 2, dim=1, keepdim=True) + torch.sum(e ** 2, dim=1) - 2 * (z @ e.t())
+        two = torch.topk(d, 2, dim=1, largest=False).values
+        gaps.append(float((two[:, 1] - two[:, 0]).min()))
+        if gaps[-1] < DPM_GAP_MIN and not watch.record_only:
+            raise _NearTie()         # (no need to finish a trajectory that is going to be redrawn)
+    watch.record_only = False
+    hook = dm.vae.vqvae.quantize.register_forward_pre_hook(watch)
+    G = dict(configs=np.array(json.dumps(DPM_FAMILY)), gap_min=np.float32(DPM_GAP_MIN),
+             toy_grid=np.array([TOY_STEP, TOY_CLAMP, TOY_GAP_MIN], dtype=np.float32))
+    toyP = toy_params()
+    G.update(toyP)
+
+    class _ToyVae:
+        quantize = staticmethod(lambda x0_: (toy_gaps.append(toy_gap(x0_)), toy_quantize(x0_))[1])
+
+    class _Toy:
+        vae = _ToyVae()
+
+        def __call__(self, x, t_input, context=None):
+            return toy_eps(toyP, x, t_input)
+    toy_gaps = []
+    for tag, kw in DPM_FAMILY:
+        skw = dict(kw)
+        # ---- (a) the real model
+        watch.record_only = tag in DPM_GUARD_UNMET
+        for seed in range(7, 7 + 400):
+            x_T = x_T0 if seed == 7 else make_inputs(2, seed=seed)[3]
+            if 't_start' in kw:          # start from the fixture's x0 noised at t_start with the fixture's noise
+                ts_ = torch.tensor([kw['t_start']])
+                nz = noise if seed == 7 else x_T          # (a redraw replaces the noise by the seed's draw)
+                x_T = ns.marginal_alpha(ts_) * x0 + ns.marginal_std(ts_) * nz
+            del gaps[:]
+            with torch.no_grad():
+                dm.model.vae = dm.vae
+                model_fn = ds.model_wrapper(model=dm.model, noise_schedule=ns, model_type='noise',
+                                            guidance_type='classifier-free', condition=slots)
+                sampler = ds.DPM_Solver(model_fn, ns, algorithm_type='dpmsolver++', correcting_x0_fn=False,
+                                        vq_denoised=True)
+                try:
+                    x, inter = sampler.sample(x_T.clone(), return_intermediate=True, **skw)
+                except _NearTie:
+                    pass
+                dm.model.vae = None
+            print(tag, 'seed', seed, 'evaluations', len(gaps), 'min gap %.3e' % min(gaps), flush=True)
+            if min(gaps) >= DPM_GAP_MIN or watch.record_only:
+                break
+        assert min(gaps) >= DPM_GAP_MIN or watch.record_only, (tag, min(gaps))
+        G[tag + '/guard_met'] = np.int32(min(gaps) >= DPM_GAP_MIN)
+        keep = _stored_states(len(inter))
+        G[tag + '/seed'], G[tag + '/gap'] = np.int32(seed), np.float32(min(gaps))
+        if 't_start' in kw:
+            G[tag + '/x_T'] = x_T                        # the noised start state (what LDM.noise_latent must give)
+            if seed != 7:
+                G[tag + '/noise'] = nz
+        elif seed != 7:
+            G[tag + '/x_T'] = x_T
+        G[tag + '/inter_idx'], G[tag + '/n_inter'] = np.array(keep, dtype=np.int32), np.int32(len(inter))
+        G[tag + '/inter'] = torch.stack([inter[i] for i in keep], 0)
+        G[tag + '/final'] = x
+        hook.remove()
+        with torch.no_grad():
+            _, _, (_, _, idx) = dm.vae.vqvae.quantize(x)
+            G[tag + '/final_idx'] = idx.to(torch.int16)
+            G[tag + '/recon_psnr'] = O.psnr(dm.vae.decode(x), img)         # per image, against the input
+        hook = dm.vae.vqvae.quantize.register_forward_pre_hook(watch)
+        # the time grid the sampler walked (restated calls of the reference's own functions)
+        sv = ds.DPM_Solver(lambda x_, t_: x_, ns, algorithm_type='dpmsolver++')
+        t_0, t_T = 1. / ns.total_N, kw.get('t_start', ns.T)
+        if kw['method'] == 'multistep':
+            G[tag + '/grid'] = sv.get_time_steps(kw.get('skip_type', 'time_uniform'), t_T, t_0, kw['steps'], 'cpu')
+        else:
+            outer, orders = sv.get_orders_and_timesteps_for_singlestep_solver(
+                kw['steps'], kw['order'], kw.get('skip_type', 'time_uniform'), t_T, t_0, 'cpu')
+            G[tag + '/grid'], G[tag + '/orders'] = outer, np.array(orders, dtype=np.int32)
+        # ---- (b) the toy model, with the model times of every evaluation
+        g = torch.Generator().manual_seed(101)
+        for tseed in range(64):
+            xt_toy = torch.randn(2, 3, 8, 8, generator=g)
+            del toy_gaps[:]
+            t_seen = []
+            toy = _Toy()
+            fn0 = ds.model_wrapper(model=toy, noise_schedule=ns, model_type='noise', guidance_type='classifier-free',
+                                   condition=slots)
+
+            def fn(x_, t_=None, quantize=False, _fn0=fn0, _seen=t_seen):
+                if not quantize:
+                    _seen.append((t_.reshape(-1)[:1] - 1. / ns.total_N) * 1000.)
+                return _fn0(x_, t_, quantize=quantize)
+            sampler = ds.DPM_Solver(fn, ns, algorithm_type='dpmsolver++', correcting_x0_fn=False, vq_denoised=True)
+            with torch.no_grad():
+                xx, tinter = sampler.sample(xt_toy.clone(), return_intermediate=True, **skw)
+            print(tag, 'toy draw', tseed, 'min rounding gap %.3e' % min(toy_gaps), 'max |x| %.3f' %
+                  max(float(i.abs().max()) for i in tinter), flush=True)
+            if min(toy_gaps) >= TOY_GAP_MIN:
+                break
+        assert min(toy_gaps) >= TOY_GAP_MIN, (tag, min(toy_gaps))
+        G[tag + '/toy_x_T'], G[tag + '/toy_inter'], G[tag + '/toy_final'] = xt_toy, torch.stack(tinter, 0), xx
+        G[tag + '/t_input'] = torch.cat(t_seen)
+    hook.remove()
+    arrs = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in G.items()}
+    path = os.path.join(OUT, 'dpm_family_b2.npz')
+    write_npz_fixed(path, arrs)
+    print('wrote dpm_family_b2.npz', os.path.getsize(path), 'bytes', {k: tuple(v.shape) for k, v in arrs.items()})
+
+
 def dino_name_map(key):
     """transformers 4.27 ViTModel key (the reference era, used by this repository's checkpoints) ->
     the key of the installed transformers 5.x ViTModel."""
@@ -722,6 +918,9 @@ def main_vqvae():
 
 
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'dpm_family':
+        main_dpm_family()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'ddim':
         main_ddim()
         sys.exit(0)
