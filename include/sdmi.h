@@ -519,6 +519,32 @@ typedef struct {
 int sdmi_st_block(const SdmiStBlockArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused SlotFormer rollout layer (bf16 inference): one pre-LN encoder layer of
+ * nn.TransformerEncoderLayer(norm_first=True, activation=relu) -- vp_vqa/models/slotformer.py:70-78 --
+ *   x += out_proj(MHA(LN1(x)));  x += linear2(relu(linear1(LN2(x))))
+ * in TWO launches (phase A: LayerNorm-fold -> q | k | v; phase B: attention, out_proj, the feed-forward streamed
+ * hidden chunk by hidden chunk), activations of a workgroup's 64 token rows resident in LDS / registers
+ * (~8 launches of sdmi_layernorm / sdmi_igemm / sdmi_attention per layer otherwise).
+ *   x, out [B][Lp][C] bf16 (out must not be x); qkv [B][Lp][3C] bf16 workspace (written by A, read by B).
+ *   C = 256, 8 heads of 32; ffn_dim a multiple of 128, <= 4C.
+ *   L real tokens per sequence in Lp rows, Lp a multiple of 64, <= 256.  Keys >= L are excluded from every
+ *     softmax; rows >= L may hold anything on entry, never influence a real row, and are written as zeros.
+ *   wstream_a / wstream_b: weights pre-packed into per-wave unit streams (sdmi_st_block's 2 KB unit format;
+ *     python: kern.WeightBank.rollout_weights).
+ *   vec_a fp32 [6C]: LayerNorm-fold column sums of q, k, v | folded biases of q, k, v.
+ *   vec_b fp32 [2C + 2 ffn_dim]: out_proj bias | fold column sums of linear1 | its folded biases | linear2 bias.
+ *   LayerNorm eps = ln_eps (1e-5), attn_scale = 32^-0.5.  phase: 0 = both launches, 1 = A only, 2 = B only.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* x; void* qkv; void* out;
+  const void* wstream_a; const float* vec_a;
+  const void* wstream_b; const float* vec_b;
+  int B, L, Lp, C, heads, ffn_dim, phase;
+  float ln_eps, attn_scale;
+} SdmiRolloutLayerArgs;
+int sdmi_rollout_layer(const SdmiRolloutLayerArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training twin of the fused SpatialTransformer block (bf16): the forward pass of
  * SpatialTransformer.forward / BasicTransformerBlock._forward / CrossAttention.forward / FeedForward
  * (video_based/models/unet/attention.py:297-308, 247-251, 182-206, 44-65) in TWO launches that also store

@@ -137,6 +137,65 @@ def transformer_predictor(K, x, num_layers, num_heads, name='predictor'):
 
 
 # ------------------------------------------------------------------------------------------
+# SlotFormer rollout: autoregressive transformer over a sliding window of slots (vp_vqa/models/slotformer.py:83-126)
+# ------------------------------------------------------------------------------------------
+ROLLOUT_TILE = 64          # token rows per workgroup of the fused layer (csrc/rollout_layer.hip)
+
+
+def rollout_pos(K, name, T, N, Lp):
+    """fp32 [Lp, D]: the temporal encoding of window position t repeated for its N slots (+ the slot encoding repeated
+    for every position), slotformer.py:99-107; rows >= T * N are zero.  Input independent, cached with the weights."""
+    wb = K.wb
+    names = tuple(n for n in (f'{name}.enc_t_pe', f'{name}.enc_slots_pe') if n in wb.t)
+    key = (names, 'rollout_pos', N, Lp)
+    if key not in wb.cache:
+        with torch.no_grad():
+            pe = wb.t[names[0]][0].float().unsqueeze(1).expand(T, N, -1)
+            if len(names) > 1:
+                pe = pe + wb.t[names[1]][0].float().unsqueeze(0)
+            out = torch.zeros((Lp, pe.shape[-1]), dtype=torch.float32, device=pe.device)
+            out[:T * N] = pe.reshape(T * N, -1)
+            wb.cache[key] = out
+    return wb.cache[key]
+
+
+def slot_rollout(K, past_slots, pred_len, num_layers, num_heads, name='rollouter', fused=False):
+    """past_slots [B, T, N, Ds] fp32 -> predicted slots [B, pred_len, N, Ds] fp32.
+
+    Every slot is projected ONCE (in_proj is row-wise, so the cached tokens equal a re-projection of the window); the
+    temporal encoding belongs to the window position and is added anew every step.  fused (bf16 inference): the window
+    lives in Lp = ceil(T N / 64) 64 rows and every layer is one sdmi_rollout_layer call (two launches); otherwise the
+    layers are the per-layer launches of transformer_predictor (autograd-recording under KernGrad: gradients flow
+    through all steps)."""
+    B, T, N, Ds = past_slots.shape
+    L = T * N
+    dt = K.wb.dtype
+    Lp = (L + ROLLOUT_TILE - 1) // ROLLOUT_TILE * ROLLOUT_TILE if fused else L
+    pe = rollout_pos(K, name, T, N, Lp)
+    ip, op = f'{name}.in_proj', f'{name}.out_proj'
+    tok = K.linear(K.cast(past_slots.reshape(B, L, Ds).contiguous(), dt), ip + '.weight', ip + '.bias')
+    D = tok.shape[-1]
+    win = tok
+    if Lp != L:            # into the padded window (pad rows may hold anything: they never reach a real row)
+        win = K.shift_window(torch.empty((B, Lp, D), dtype=tok.dtype, device=tok.device), tok, L)
+    preds = []
+    for step in range(pred_len):
+        x = K.add_pos(win, pe)
+        if fused:
+            for i in range(num_layers):
+                x = K.rollout_layer(x, f'{name}.transformer_encoder.layers.{i}', L, num_heads)
+                assert x is not None, 'the caller checks that the layers qualify for the fused kernel'
+        else:
+            x = transformer_predictor(K, x, num_layers, num_heads, name=name)
+        pred = K.linear(K.tail_tokens(x, N, L), op + '.weight', op + '.bias', out_dtype=torch.float32)
+        preds.append(pred)
+        if step + 1 < pred_len:
+            new = K.linear(K.cast(pred, dt), ip + '.weight', ip + '.bias')
+            win = K.shift_window(win, new, L)
+    return K.stack_time(preds)
+
+
+# ------------------------------------------------------------------------------------------
 # a9-a11: LDM UNet (unet.py:551-576, 271-285; attention.py:297-308, 247-251, 182-206)
 # ------------------------------------------------------------------------------------------
 class UNetRunner:

@@ -69,6 +69,7 @@ _ST_FUSED = bool(policy.flag('ST_FUSED'))     # fused SpatialTransformer block (
 _ST_FF_SPLIT = bool(policy.flag('ST_FF_SPLIT'))   # ... its feed-forward over workgroup pairs where the grid is half the chip
 _WGRAD_HALO = bool(policy.flag('WGRAD_HALO'))    # direct 3x3 weight gradient on channel pairs (wgrad3x3_halo_kernel)
 _CROSS_ONE = 64            # folded slot cross-attention as ONE launch (sdmi_cross_fold) up to this many tokens per image
+_ROLLOUT_FUSED = bool(policy.flag('ROLLOUT_FUSED'))   # fused SlotFormer rollout layer (sdmi_rollout_layer)
 _UPS_PARITY = bool(policy.flag('UPS_PARITY'))   # upsample convolutions as four 2x2 parity convolutions in one launch
 # the fused inference block only when its grid (one workgroup per 64 / 32 token rows) fills a good part of the chip: at
 # B = 64 the 8^2 level gives 64 workgroups that each stream the block's 4 MB of weights -- 119 us against 108 us for the
@@ -165,6 +166,28 @@ def st_index_img(C):
         for k2 in range(2):
             for s_ in range(g['NSL']):
                 e.append((128 * C, 128, (w * g['NSL'] + s_) * 16, k2 * 64))
+        ent.append(e)
+    return _st_unit_index(ent)
+
+
+def rollout_index_a(C=256):
+    """Phase A of the fused rollout layer (csrc/rollout_layer.hip): source = [W_q' | W_k' | W_v'] (3C x C) flat."""
+    NSL, KT = C // 128, C // 64
+    return _st_unit_index([[(m * C * C, C, (w * NSL + s_) * 16, kt * 64)
+                            for m in range(3) for kt in range(KT) for s_ in range(NSL)] for w in range(8)])
+
+
+def rollout_index_b(C, F):
+    """Phase B source = [W_o (C x C) | W_1' (F x C) | W_2 (C x F)] flat: out_proj, then per hidden chunk of 128 the
+    chunk's linear1 rows and its 128 k of linear2."""
+    NSL, KT = C // 128, C // 64
+    o1, o2 = C * C, C * C + F * C
+    ent = []
+    for w in range(8):
+        e = [(0, C, (w * NSL + s_) * 16, kt * 64) for kt in range(KT) for s_ in range(NSL)]
+        for hc in range(F // 128):
+            e += [(o1, C, hc * 128 + w * 16, kt * 64) for kt in range(KT)]
+            e += [(o2, F, (w * NSL + s_) * 16, hc * 128 + k2 * 64) for k2 in range(2) for s_ in range(NSL)]
         ent.append(e)
     return _st_unit_index(ent)
 
@@ -779,6 +802,37 @@ class WeightBank:
                 self.cache[key] = dict(wa=wa, va=vec_a, wb=wbs, vb=vec_b, C=C)
         return self.cache[key]
 
+    def rollout_weights(self, l, dtype):
+        """Packed operands of the fused rollout layer `l` (sdmi.h: sdmi_rollout_layer): the unit streams of phase A / B
+        and their fp32 epilogue vectors, LayerNorm gamma folded into the weights and beta into the biases as in
+        ln_folded.  Weight preparation, cached until the weights change."""
+        key = ('rollout', l, dtype)
+        if key not in self.cache:
+            with torch.no_grad():
+                f = lambda k: self.t[l + k].float()
+                wqkv, bqkv = f('.self_attn.in_proj_weight'), f('.self_attn.in_proj_bias')
+                C = wqkv.shape[1]
+                dev = wqkv.device
+                g1, b1 = f('.norm1.weight'), f('.norm1.bias')
+                wqkv_p = (wqkv * g1).to(dtype)
+                ia = self.cache.get(('rollout_index', 'a', C))
+                if ia is None:
+                    ia = self.cache[('rollout_index', 'a', C)] = rollout_index_a(C).to(dev)
+                wa = wqkv_p.reshape(-1)[ia].contiguous()
+                va = torch.cat([wqkv_p.float().sum(1), wqkv @ b1 + bqkv]).contiguous()
+                wo, bo = f('.self_attn.out_proj.weight'), f('.self_attn.out_proj.bias')
+                g2, b2 = f('.norm2.weight'), f('.norm2.bias')
+                w1, bb1, w2, bb2 = f('.linear1.weight'), f('.linear1.bias'), f('.linear2.weight'), f('.linear2.bias')
+                F = w1.shape[0]
+                w1_p = (w1 * g2).to(dtype)
+                ib = self.cache.get(('rollout_index', 'b', C, F))
+                if ib is None:
+                    ib = self.cache[('rollout_index', 'b', C, F)] = rollout_index_b(C, F).to(dev)
+                src_b = torch.cat([wo.to(dtype).reshape(-1), w1_p.reshape(-1), w2.to(dtype).reshape(-1)])
+                vb = torch.cat([bo, w1_p.float().sum(1), w1 @ b2 + bb1, bb2]).contiguous()
+                self.cache[key] = dict(wa=wa, va=va, wb=src_b[ib].contiguous(), vb=vb, C=C, F=F)
+        return self.cache[key]
+
     # ---- weight streams of the fused SpatialTransformer TRAINING kernels (sdmi.h: sdmi_st_train_fwd, sdmi_st_pack)
     def st_train_mats(self, n):
         """{key: (bf16 operand view [N][K], K)} of block `n` straight out of the shadow arena."""
@@ -1245,11 +1299,41 @@ class Kern:
             ops._PENDING[out.data_ptr()] = ops._PendingSplit(out, kw, 2, (part, bias, None, x, 1.0))
         return out
 
+    def rollout_layer(self, x, l, L, heads):
+        """One pre-LN encoder layer `l` of the SlotFormer rollouter in two launches (sdmi.h: sdmi_rollout_layer) -- bf16
+        inference, x [B, Lp, 256] with L real tokens per sequence in Lp rows (a multiple of 64, <= 256), 8 heads of 32,
+        ffn_dim a multiple of 128 up to 1024.  None when the layer does not qualify (the caller runs the per-layer
+        launches)."""
+        B, Lp, C = x.shape
+        w1 = self.wb.t[l + '.linear1.weight']
+        F = w1.shape[0]
+        if not (_ROLLOUT_FUSED and x.dtype == torch.bfloat16 and x.is_contiguous() and C == 256 and heads == 8 and
+                Lp % 64 == 0 and Lp <= 256 and 1 <= L <= Lp and F % 128 == 0 and F <= 4 * C):
+            return None
+        wts = self.wb.rollout_weights(l, x.dtype)
+        qkv = torch.empty((B, Lp, 3 * C), dtype=x.dtype, device=x.device)
+        out = torch.empty_like(x)
+        flops = 2.0 * B * Lp * (4 * C * C + 2 * C * F) + 4.0 * B * Lp * L * C
+        call('sdmi_rollout_layer', _st(), x=_p(x), qkv=_p(qkv), out=_p(out), wstream_a=_p(wts['wa']), vec_a=_p(wts['va']),
+             wstream_b=_p(wts['wb']), vec_b=_p(wts['vb']), B=B, L=L, Lp=Lp, C=C, heads=heads, ffn_dim=F, phase=0,
+             ln_eps=1e-5, attn_scale=32.0 ** -0.5,
+             _meta=dict(flops=flops, bytes=2.0 * B * Lp * C * 2 + 2.0 * (wts['wa'].numel() + wts['wb'].numel())))
+        return out
+
     def geglu(self, h):
         return ops.geglu(h)
 
     def add_pos(self, x, pos):
         return ops.add_pos(x, pos)
+
+    def shift_window(self, win, new, L):
+        return shift_window(win, new, L)
+
+    def tail_tokens(self, x, n, L):
+        return tail_tokens(x, n, L)
+
+    def stack_time(self, xs):
+        return StackTimeFn.apply(*xs)
 
     def rowvec_slices(self, rowvecs, bounds):
         """[B, total] -> {i: rowvecs[:, off:off+c]} (strided views; the kernels take the row pitch)."""
@@ -2314,6 +2398,71 @@ class StackTimeFn(torch.autograd.Function):
         return tuple(outs)
 
 
+def _copy_rows(src, src_off, lds, dst, dst_off, ldd, B, cols):
+    """dst[b][dst_off .. + cols] = src[b][src_off .. + cols] for b < B (element offsets / pitches; same dtype)."""
+    es, dt = src.element_size(), _DT[src.dtype]
+    call('sdmi_cast2d', _st(), src=src.data_ptr() + src_off * es, dst=dst.data_ptr() + dst_off * es, src_dtype=dt,
+         dst_dtype=dt, rows=B, cols=cols, lds=lds, ldd=ldd, zpad=0)
+
+
+def shift_window(win, new, L):
+    """Sliding window of the SlotFormer rollout (slotformer.py:124): win [B, Lp, D] holds L real token rows, new
+    [B, N, D] -> out rows [0, L - N) = win rows [N, L), rows [L - N, L) = new.  Rows >= L are left unwritten (pad rows
+    of the fused layer's operand may hold anything)."""
+    B, Lp, D = win.shape
+    N = new.shape[1]
+    out = torch.empty_like(win)
+    if L > N:
+        _copy_rows(win, N * D, Lp * D, out, 0, Lp * D, B, (L - N) * D)
+    _copy_rows(new.contiguous(), 0, N * D, out, (L - N) * D, Lp * D, B, N * D)
+    return out
+
+
+def tail_tokens(x, n, L):
+    """x [B, Lp, D] -> contiguous [B, n, D] = rows [L - n, L) (slotformer.py:120: the last N output tokens)."""
+    B, Lp, D = x.shape
+    out = torch.empty((B, n, D), dtype=x.dtype, device=x.device)
+    _copy_rows(x, (L - n) * D, Lp * D, out, 0, n * D, B, n * D)
+    return out
+
+
+class ShiftWindowFn(torch.autograd.Function):
+    """shift_window with its gradient: d win rows [N, L) = d out rows [0, L - N) (the dropped rows get zero),
+    d new = d out rows [L - N, L)."""
+
+    @staticmethod
+    def forward(ctx, win, new, L):
+        ctx.geo = (L, new.shape[1])
+        return shift_window(win, new, L)
+
+    @staticmethod
+    def backward(ctx, dout):
+        L, N = ctx.geo
+        dout = dout.contiguous()
+        B, Lp, D = dout.shape
+        dwin = ops.zeros(dout.shape, dout.dtype, dout.device)
+        if L > N:
+            _copy_rows(dout, 0, Lp * D, dwin, N * D, Lp * D, B, (L - N) * D)
+        return dwin, tail_tokens(dout, N, L), None
+
+
+class TailTokensFn(torch.autograd.Function):
+    """tail_tokens with its gradient (zero outside the rows taken)."""
+
+    @staticmethod
+    def forward(ctx, x, n, L):
+        ctx.geo = (tuple(x.shape), n, L)
+        return tail_tokens(x, n, L)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (B, Lp, D), n, L = ctx.geo
+        dy = dy.contiguous()
+        dx = ops.zeros((B, Lp, D), dy.dtype, dy.device)
+        _copy_rows(dy, 0, n * D, dx, (L - n) * D, Lp * D, B, n * D)
+        return dx, None, None
+
+
 class VaeAttnFn(torch.autograd.Function):
     """Core of the VQ-VAE AttnBlock (vqvae/modules.py:130-150): one head of width C over S tokens,
     qkv [B,S,3C] -> o [B,S,C], as batched GEMMs (S = q k^T, P = softmax(S / sqrt(C)), o = P v) with
@@ -2717,6 +2866,12 @@ class KernGrad(Kern):
 
     def add_pos(self, x, pos):
         return AddPosFn.apply(x, pos)
+
+    def shift_window(self, win, new, L):
+        return ShiftWindowFn.apply(win, new, L)
+
+    def tail_tokens(self, x, n, L):
+        return TailTokensFn.apply(x, n, L)
 
     def concat(self, a, b):
         return ConcatFn.apply(a, b)

@@ -42,6 +42,26 @@ class SyntheticDataModule:
             yield {'img': (torch.randn(shape, generator=g) * 0.5).clamp_(-1, 1).to(self.device)}
 
 
+class SyntheticSlotsDataModule:
+    """`build_dataset` stand-in of the vp_vqa task: seeded random slots [B, history + rollout, N, D] (the Physion slots
+    reader is out of scope; the model consumes pre-extracted slots, vp_vqa/datasets/physion.py)."""
+
+    def __init__(self, params, steps_per_epoch=8, device='cuda', seed=1234):
+        self.params, self.steps_per_epoch, self.device, self.seed = params, steps_per_epoch, device, seed
+        self.rank = int(os.environ.get('RANK', 0))
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def train_loader(self, epoch=0):
+        p = self.params
+        T = p.rollout_dict['history_len'] + p.loss_dict['rollout_len']
+        shape = (p.train_batch_size, T, p.slot_dict['num_slots'], p.slot_dict['slot_size'])
+        g = torch.Generator().manual_seed(self.seed + 1000 * epoch + self.rank)
+        for _ in range(self.steps_per_epoch):
+            yield {'slots': torch.randn(shape, generator=g).to(self.device)}
+
+
 class Method:
     """fit() = epochs x steps of {forward, weighted loss, backward, (all-reduce), clip+Adam, hook}."""
 
@@ -72,8 +92,9 @@ class Method:
         # schedule floor: the diffusion methods anneal to 0 (img_based/method.py:277-283,
         # video_based/method.py:186-194 / 331-339); SA / SAVi / VQ-VAE stage 1 run on the base
         # method's schedule, min_lr = lr / 100 (img_based/method.py:69-85, video_based/method.py:86-96)
-        from .models import SADiffusion, SAViDiffusion
-        diffusion = isinstance(self.model, (SADiffusion, SAViDiffusion))
+        # (vp_vqa/method.py:72-90: the SlotFormer task runs on the base schedule too, min_lr = lr / 100, one group at lr)
+        from .models import LDMSlotFormer, SADiffusion, SAViDiffusion
+        diffusion = isinstance(self.model, (SADiffusion, SAViDiffusion)) and not isinstance(self.model, LDMSlotFormer)
         return FusedAdam(self.model, lr=p.lr, dec_lr=self._get('dec_lr', p.lr), clip_grad=clip,
                          total_steps=total, warmup_pct=p.warmup_steps_pct,
                          min_lr_ratio=(0.0 if diffusion else 0.01))
@@ -140,6 +161,8 @@ class Method:
 
     def _loss_names(self):
         from .models import SA, VQVAE
+        if getattr(self.model, 'loss_names', None):       # LDMSlotFormer: slot_recon_loss
+            return list(self.model.loss_names)
         if isinstance(self.model, VQVAE):        # three weighted terms: eager steps (vqvae/loss.py)
             return ['quant_loss', 'recon_loss', 'percept_loss']
         return ['img_recon_loss'] if isinstance(self.model, SA) else ['denoise_loss']

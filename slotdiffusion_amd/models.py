@@ -5,6 +5,7 @@ evaluation scripts can switch packages:
   SADiffusion ............ slotdiffusion/img_based/models/sa_diffusion.py:73-246
   LDM (model.dm_decoder) . slotdiffusion/img_based/models/ddpm/ldm.py:18-129, cond_ddpm.py:134-212
   VQVAEWrapper (.vae) .... slotdiffusion/video_based/models/vqvae/VQVAE.py:152-194
+  LDMSlotFormer .......... slotdiffusion/vp_vqa/models/ldm_slotformer.py:14-215, slotformer.py:46-126
 Tensors cross this boundary in the reference's layout (NCHW fp32 images / latents, [B,N,D] slots);
 inside, everything is NHWC in the compute dtype (fp32 for parity runs, bf16 for throughput).
 """
@@ -1045,6 +1046,169 @@ class VQVAE(SlotModelBase):
         return loss_dict
 
 
+class LDMSlotFormer(SADiffusion):
+    """SlotFormer with the LDM slot decoder (registry name 'LDMSlotFormer', vp_vqa/models/ldm_slotformer.py:14-215):
+    an autoregressive transformer (SlotRollouter, slotformer.py:46-126) predicts future slots from a window of
+    `history_len` burn-in frames; the frozen slot-conditioned LDM of a SAViDiffusion checkpoint decodes them to frames.
+    Training is the slot reconstruction loss over `rollout_len` predicted frames; the decoder never trains."""
+    loss_names = ['slot_recon_loss']
+
+    def __init__(self, resolution, clip_len, slot_dict, dec_dict, rollout_dict, loss_dict, eps=1e-6,
+                 compute_dtype=None, seed=0):
+        loss_dict = dict(loss_dict)
+        for k in ('use_denoise_loss', 'use_img_recon_loss'):
+            # (use_denoise_loss fails in the reference too: calc_train_loss reads out_dict['slots'], which forward
+            # never sets, ldm_slotformer.py:159-185; the image loss would back-propagate through the sampler)
+            if loss_dict.get(k, False):
+                raise ValueError(f"loss_dict['{k}']=True is not on the MI355X hot path: LDMSlotFormer trains on "
+                                 "slot_recon_loss only")
+        dec_dict = copy.deepcopy(dec_dict)
+        weight_path = dec_dict.pop('dec_ckp_path', '')
+        dd = dec_dict['diffusion_dict']
+        sp = spec.ldm_slotformer(slot_dict, dec_dict, rollout_dict)
+        sched = {k: dd[k] for k in ('timesteps', 'beta_schedule', 'linear_start', 'linear_end') if k in dd}
+        FlatModule.__init__(self, sp, schedule_kwargs=sched, seed=seed,
+                            node_classes={'dm_decoder': LDM, 'dm_decoder.vae': VQVAEWrapper})
+        assert dd.get('pred_target', 'eps') in ('eps', 'x0', 'v')
+        self.dm_decoder.pred_target = dd.get('pred_target', 'eps')
+        self.resolution, self.clip_len, self.eps = tuple(resolution), clip_len, eps
+        self.slot_dict, self.dec_dict = dict(slot_dict), dec_dict
+        self.rollout_dict, self.loss_dict = dict(rollout_dict), loss_dict
+        self.num_slots, self.slot_size = slot_dict['num_slots'], slot_dict['slot_size']
+        self.history_len = rollout_dict['history_len']
+        self.rollout_len = loss_dict['rollout_len']
+        self.use_img_recon_loss = self.use_denoise_loss = False
+        self.latent_res = tuple(dec_dict['resolution'])
+        self.ed = dec_dict['vae_dict']['enc_dec_dict']
+        self.z_scale = float(dd.get('z_scale_factor', 1.))
+        self.vq_key = 'dm_decoder.vae.vqvae.quantize.embedding.weight'
+        self.unet_cfg = dec_dict['unet_dict']
+        self.testing = False
+        self.loss_decay_factor = 1.
+        self.train_dropout = 0.0           # the decoder is frozen and stays in eval mode
+        self.pred_dropout = 0.1            # nn.TransformerEncoderLayer default (slotformer.py:70-76)
+        self.compute_dtype = compute_dtype or default_compute_dtype()
+        self.dm_decoder._bind(self)
+        self.dm_decoder.vae._bind(self)
+        self._bank = self._unet = None
+        self._plans = {}
+        self._Kinf = self._Kgrad = None
+        self.step_seed = self.eval_seed = None
+        self.use_graph = os.environ.get('SDMI_GRAPH', '1') != '0'
+        self._graph_cache = {}
+        self.dm_decoder.eval()
+        if weight_path and os.path.exists(weight_path):       # ldm_slotformer.py:123-131
+            self.load_decoder_weight(weight_path)
+        elif weight_path:
+            print(f'Warning: DM decoder weight not found at {weight_path}!!!')
+
+    @property
+    def device(self):
+        return self.rollouter.in_proj.weight.device
+
+    @property
+    def dtype(self):
+        return self.rollouter.in_proj.weight.dtype
+
+    def load_decoder_weight(self, path):
+        """The `dm_decoder.` tensors of a SAViDiffusion checkpoint (ldm_slotformer.py:124-129); every decoder key
+        must be there."""
+        w = torch.load(path, map_location='cpu')
+        w = w.get('state_dict', w)
+        w = {k: v for k, v in w.items() if k.startswith('dm_decoder.')}
+        missing, unexpected = self.load_state_dict(w, strict=False)
+        bad = [k for k in missing if k.startswith('dm_decoder.')] + list(unexpected)
+        if bad:
+            raise RuntimeError(f'{path}: decoder keys do not match (first: {bad[:3]})')
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.dm_decoder.eval()             # keep the decoder part in eval mode (ldm_slotformer.py:187-191)
+        return self
+
+    # -- rollout -------------------------------------------------------------------------
+    def _fused_ok(self):
+        """bf16 evaluation on the fused layer kernel (sdmi.h: sdmi_rollout_layer): d_model 256 in 8 heads of 32,
+        the window within 256 rows, ffn_dim a multiple of 128 up to 4 d_model.  Anything else: per-layer launches."""
+        r = self.rollout_dict
+        return (kern._ROLLOUT_FUSED and self.compute_dtype == torch.bfloat16 and not self.training and
+                r['d_model'] == 256 and r['num_heads'] == 8 and r['history_len'] * r['num_slots'] <= 256 and
+                r['ffn_dim'] % 128 == 0 and r['ffn_dim'] <= 1024)
+
+    def _rollout_slots(self, past, pred_len):
+        """past [B, history_len, N, D] fp32 contiguous -> [B, pred_len, N, D] fp32 (slotformer.py:83-126)."""
+        r = self.rollout_dict
+        grad = self.training and torch.is_grad_enabled()
+        fused = not grad and self._fused_ok()
+        run = lambda x: engine.slot_rollout(self.KG() if grad else self.K(), x, pred_len, r['num_layers'],
+                                            r['num_heads'], fused=fused)
+        if grad:
+            return run(past)
+        with torch.no_grad():
+            if not (fused and self.use_graph):
+                return run(past)
+            # all pred_len steps (7 + 2 num_layers launches each) captured once per (B, pred_len) and replayed
+            key = ('rollout', tuple(past.shape), pred_len)
+            g = self._graph_cache.get(key)
+            if g is None:
+                sp = torch.empty_like(past)
+                sp.copy_(past)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):            # warm-up: weight packing, func attributes
+                    run(sp)
+                torch.cuda.current_stream().wait_stream(side)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                    out = run(sp)
+                g = self._graph_cache[key] = (graph, sp, out)
+            graph, sp, out = g
+            sp.copy_(past)
+            graph.replay()
+            return out.clone()
+
+    def rollout(self, past_slots, pred_len, decode=False, with_gt=True):
+        """ldm_slotformer.py:136-157: predicted slots [B, pred_len, N, D]; decode=True also samples the frames of
+        the predicted (with_gt: burn-in + predicted) slots through the LDM."""
+        past = past_slots[:, -self.history_len:]
+        assert past.shape[1] == self.history_len, 'wrong burn-in steps'
+        pred_slots = self._rollout_slots(past.contiguous().float(), pred_len)
+        if not decode:
+            return pred_slots
+        slots = torch.cat([past_slots.float(), pred_slots], dim=1) if with_gt else pred_slots
+        B, T = slots.shape[:2]
+        log_dict = self.log_images({'slots': slots.flatten(0, 1)}, use_dpm=True, same_noise=True)
+        return {'recon_combined': log_dict['samples'].unflatten(0, (B, T)), 'slots': slots}
+
+    def forward(self, data_dict):
+        """ldm_slotformer.py:159-171."""
+        slots = data_dict['slots']
+        assert self.rollout_len + self.history_len == slots.shape[1], \
+            f'wrong SlotFormer training length {slots.shape[1]}'
+        self._begin_train_forward()
+        pred_slots = self.rollout(slots[:, :self.history_len], self.rollout_len)
+        return {'gt_slots': slots[:, self.history_len:], 'pred_slots': pred_slots}
+
+    def calc_train_loss(self, data_dict, out_dict):
+        """ldm_slotformer.py:173-185: {'slot_recon_loss': mse(pred_slots, gt_slots)}."""
+        pred, gt = out_dict['pred_slots'], out_dict['gt_slots'].float().contiguous()
+        if pred.requires_grad:
+            return {'slot_recon_loss': kern.MseFn.apply(pred, gt, 1.0)}
+        return {'slot_recon_loss': ops.mse(pred.contiguous(), gt).reshape(())}
+
+    @torch.no_grad()
+    def log_images(self, data_dict, **kwargs):
+        """ldm_slotformer.py:193-215: slots [T, N, D] -> {'samples': decoded frames [T, 3, H, W]}."""
+        slots = data_dict['slots']
+        z = self.dm_decoder.generate_imgs(slots, batch_size=slots.shape[0], **kwargs)
+        if isinstance(z, tuple):
+            z = z[0]
+        return {'samples': self.dm_decoder.vae.decode(z)}
+
+    def _training_step_end(self, method=None):
+        pass
+
+
 def build_model(params):
     """Registry (img_based/models/__init__.py:12-39, video_based/models/__init__.py:12-33) for the
     hot-path models."""
@@ -1066,4 +1230,8 @@ def build_model(params):
         return SADiffusion(resolution=params.resolution, slot_dict=params.slot_dict,
                            enc_dict=params.enc_dict, dec_dict=params.dec_dict,
                            loss_dict=params.loss_dict)
+    if params.model == 'LDMSlotFormer':        # vp_vqa/models/__init__.py:9-18
+        return LDMSlotFormer(resolution=params.resolution, clip_len=params.input_frames,
+                             slot_dict=params.slot_dict, dec_dict=params.dec_dict,
+                             rollout_dict=params.rollout_dict, loss_dict=params.loss_dict)
     raise NotImplementedError(f'{params.model} is not on the MI355X hot path yet')

@@ -71,6 +71,15 @@ def build_grid(resolution):
     return torch.cat([g, 1. - g], dim=-1)
 
 
+def sin_pos_enc(seq_len, d_model):
+    """[1, L, D] sinusoid over REVERSED positions L-1 .. 0 (vp_vqa/models/slotformer.py:8-14; same torch CPU ops, so
+    the values are the reference's bit for bit)."""
+    inv_freq = 1. / (10000 ** (torch.arange(0.0, d_model, 2.0) / d_model))
+    pos_seq = torch.arange(seq_len - 1, -1, -1).type_as(inv_freq)
+    sinusoid_inp = torch.outer(pos_seq, inv_freq)
+    return torch.cat([sinusoid_inp.sin(), sinusoid_inp.cos()], dim=-1).unsqueeze(0)
+
+
 def _init_tensor(p, gen, sched):
     shape = p.shape
     if p.init.startswith('buf:'):
@@ -85,6 +94,8 @@ def _init_tensor(p, gen, sched):
     elif p.init == 'kfo':
         fan_out = shape[0] * shape[2] * shape[3]
         t.normal_(0., math.sqrt(2. / fan_out), generator=gen)
+    elif p.init == 'sinpe':
+        t.copy_(sin_pos_enc(shape[1], shape[2]))
     elif p.init == 'one':
         t.fill_(1.)
     elif p.init in ('zero', 'zlin'):

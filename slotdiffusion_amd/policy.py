@@ -17,6 +17,7 @@ SWITCHES = {
     'UPS_PARITY':    (1, 'upsample convolutions as four 2x2 parity convolutions in one launch'),
     'DEFER_SPLITK':  (1, 'split-K second stage finished by the GroupNorm behind the convolution'),
     'LAZY_CAT':      (1, 'UNet skip concatenations read in place by their two consumers'),
+    'ROLLOUT_FUSED': (1, 'fused SlotFormer rollout layer at inference (sdmi_rollout_layer: 2 launches instead of ~8)'),
     # --- training
     'ST_TRAIN':      (1, 'fused training forward of the SpatialTransformer block (sdmi_st_train_fwd)'),
     'ST_TRAIN_BWD':  (1, 'fused backward data path of that block (sdmi_st_train_bwd)'),

@@ -21,6 +21,7 @@ Reference layouts restated (names only, no code shared):
   VQVAE wrapper ............. video_based/models/vqvae/VQVAE.py:66-82
   DDPM schedule buffers ..... video_based/models/ddpm/ddpm.py:69-131
   TransformerPredictor ...... video_based/models/predictor.py:20-44
+  SlotRollouter ............. vp_vqa/models/slotformer.py:46-81
 """
 from collections import namedtuple
 
@@ -29,6 +30,7 @@ from collections import namedtuple
 #  'kfo'   kaiming-normal, fan_out, relu gain (ResNet convs, resnet.py:238-241)
 #  'one'/'zero'  constants;  'zlin' = zero-initialised layer (zero_module)
 #  'n01'   N(0,1);  'vq' U(+-1/n_e);  'gru' U(+-1/sqrt(hidden)); 'xav' xavier-U
+#  'sinpe' frozen sinusoid over reversed positions (module.sin_pos_enc)
 #  'buf:*' non-trainable buffers computed by module.py
 P = namedtuple('P', 'name shape init fan_in trainable')
 
@@ -466,3 +468,30 @@ def savi_diffusion(resolution, slot_dict, enc_dict, dec_dict, pred_dict):
                                  in pred_dict else slot_dict['slot_size'],
                                  pred_dict['pred_num_layers'], pred_dict['pred_ffn_dim'])
     return head + rest + ldm('dm_decoder', dec_dict) + pred
+
+
+def slot_rollouter(name, rollout_dict):
+    """SlotRollouter (vp_vqa/models/slotformer.py:46-81) in state_dict order: the module's own parameters (the
+    positional encodings) come before its children's."""
+    r = rollout_dict
+    d, T, N = r['d_model'], r['history_len'], r['num_slots']
+    for k in ('t_pe', 'slots_pe'):
+        assert r.get(k, '') == '' or 'sin' in r[k], \
+            f'{k}={r[k]!r}: learnable positional encodings are not on the MI355X hot path yet'
+    assert r.get('t_pe', 'sin'), 'the temporal encoding must not be empty (slotformer.py:99)'
+    assert r.get('norm_first', True), 'the hot path covers the pre-LN rollouter (norm_first=True, every shipped config)'
+    out = [_p(f'{name}.enc_t_pe', (1, T, d), 'sinpe', trainable=False)]
+    if r.get('slots_pe', ''):
+        out.append(_p(f'{name}.enc_slots_pe', (1, N, d), 'sinpe', trainable=False))
+    out += linear(f'{name}.in_proj', r['slot_size'], d)
+    out += transformer_predictor(name, d, r['num_layers'], r['ffn_dim'])
+    out += linear(f'{name}.out_proj', d, r['slot_size'])
+    return out
+
+
+def ldm_slotformer(slot_dict, dec_dict, rollout_dict):
+    """LDMSlotFormer (vp_vqa/models/ldm_slotformer.py:14-134, slotformer.py:182-185: decoder, then rollouter): the
+    frozen slot-conditioned LDM followed by the SlotRollouter."""
+    assert rollout_dict['slot_size'] == slot_dict['slot_size'] and rollout_dict['num_slots'] == slot_dict['num_slots']
+    dec = [p._replace(trainable=False) for p in ldm('dm_decoder', dec_dict)]
+    return dec + slot_rollouter('rollouter', rollout_dict)

@@ -1,0 +1,18 @@
+"""Registry module with the surface of `slotdiffusion.vp_vqa` (scripts/train.py:97-100): video prediction with
+LDMSlotFormer.  The Physion readout / VQA models stay out of scope."""
+from .. import models as _models
+from ..method import SyntheticSlotsDataModule, build_method  # noqa: F401
+
+
+def build_model(params):
+    """vp_vqa/models/__init__.py:9-22."""
+    if params.model == 'LDMSlotFormer':
+        return _models.LDMSlotFormer(resolution=params.resolution, clip_len=params.input_frames,
+                                     slot_dict=params.slot_dict, dec_dict=params.dec_dict,
+                                     rollout_dict=params.rollout_dict, loss_dict=params.loss_dict)
+    raise NotImplementedError(f'{params.model} is not on the MI355X hot path yet')
+
+
+def build_dataset(params, val_only=False):
+    """Datasets are out of scope; synthetic slots [B, history + rollout, N, D]."""
+    return SyntheticSlotsDataModule(params)

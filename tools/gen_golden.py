@@ -917,7 +917,62 @@ def main_vqvae():
     print('wrote vqvae_b2.npz', {k: (tuple(v.shape), float(v.flatten()[0])) for k, v in G.items()})
 
 
+def main_slotformer():
+    """tests/golden/ldmslotformer_b2.npz + tests/golden/vp_vqa/ldmslotformer_keys.json.gz: the reference's third task
+    (vp_vqa: LDMSlotFormer).  Keys: the shipped config (12 layers).  Fixture: the shipped config with num_layers=2 and
+    rollout_len=3 (15 x 8 tokens, slot size 192, d_model 256, 8 heads, ffn 1024), det-filled, the rollouter in eval mode
+    (dropout off), B = 2 seeded slots [2, 18, 8, 192]: pred_slots, slot_recon_loss, gradient norms of every trainable
+    tensor and three gradient tensors (the in_proj_weight one as every 4th row)."""
+    import gzip
+    import json
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    vm = rh.ref_models('vp_vqa')
+    skip = lambda n: is_buffer_name(n) or n.endswith('enc_t_pe')        # the frozen sinusoid keeps its values
+    P = rh.ref_params('vp_vqa', '', 'ldmslotformer_physion_params-res128')
+    model = vm.build_model(P)
+    keys = {'state': [[k, list(v.shape)] for k, v in model.state_dict().items()],
+            'frozen': [k for k, v in model.named_parameters() if not v.requires_grad]}
+    os.makedirs(os.path.join(OUT, 'vp_vqa'), exist_ok=True)
+    with open(os.path.join(OUT, 'vp_vqa', 'ldmslotformer_keys.json.gz'), 'wb') as f:
+        with gzip.GzipFile(fileobj=f, mode='wb', mtime=0) as gz:        # (mtime=0: the file regenerates bit-identically)
+            gz.write(json.dumps(keys, sort_keys=True).encode())
+    del model
+    P = rh.ref_params('vp_vqa', '', 'ldmslotformer_physion_params-res128')
+    P.rollout_dict['num_layers'] = 2
+    P.loss_dict['rollout_len'] = 3
+    model = vm.build_model(P)
+    det_fill_(model.state_dict().items(), skip=skip)
+    B, T, N, D = 2, P.rollout_dict['history_len'] + 3, P.num_slots, P.slot_size
+    slots = torch.randn(B, T, N, D, generator=torch.Generator().manual_seed(29))
+    model.train()
+    model.rollouter.eval()                  # dropout of nn.TransformerEncoderLayer off
+    for p in model.parameters():
+        p.grad = None
+    out = model(dict(slots=slots))
+    loss = model.calc_train_loss(dict(slots=slots), out)['slot_recon_loss']
+    loss.backward()
+    G = dict(slots=slots, pred_slots=out['pred_slots'].detach(), slot_recon_loss=loss.detach())
+    named = dict(model.named_parameters())
+    names = sorted(n for n, p in named.items() if p.requires_grad)
+    assert all(named[n].grad is not None for n in names)
+    G['grad_norms_names'] = np.array(names)
+    G['grad_norms'] = torch.tensor([float(named[n].grad.norm()) for n in names])
+    for n in ['rollouter.in_proj.weight', 'rollouter.out_proj.bias']:
+        G['grad:' + n] = named[n].grad.detach().clone()
+    # (every 4th row of the [768, 256] q | k | v gradient -- rows of all three parts; the whole tensor alone is 786 KB)
+    n = 'rollouter.transformer_encoder.layers.1.self_attn.in_proj_weight'
+    G['grad_rows4:' + n] = named[n].grad.detach()[::4].clone()
+    arrs = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in G.items()}
+    np.savez_compressed(os.path.join(OUT, 'ldmslotformer_b2.npz'), **arrs)
+    for k, v in arrs.items():
+        print(k, v.shape, v.dtype)
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'slotformer':
+        main_slotformer()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'dpm_family':
         main_dpm_family()
         sys.exit(0)
