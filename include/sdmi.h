@@ -432,6 +432,40 @@ typedef struct {
 int sdmi_dpm_step(const SdmiDpmStepArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The tail of ONE function evaluation of UniPC (Zhao et al. 2023; multistep, data-prediction form, orders 1-3,
+ * coefficients folded on the host: slotdiffusion_amd/unipc.py) in one launch.  Evaluation n, at time t_n:
+ *   data prediction from the evaluated state x and the network output `out` (target, sigma, alpha: as sdmi_dpm_step)
+ *   -> VQ nearest code (the same search, the same indices) -> m0, the quantised prediction (idx optional)
+ *   -> corrector of the step just taken, corr_order 1..3 (0: none), from `base` = the carried state at t_{n-1} and the
+ *      predictions h1, h2, h3 of the one, two and three evaluations before:
+ *        v = c0*base + c1*h1;  v = v + w1*(h2 - h1)  (order >= 2);  v = v + w2*(h3 - h1)  (order 3);
+ *        xc = v + wn*(m0 - h1)
+ *   -> predictor of the next step, pred_order 1..3 (0: none), from s = xc (without corrector: s = base, which is then
+ *      the carried state at t_n):
+ *        v = p0*s + p1*m0;  v = v + q1*(h1 - m0)  (order >= 2);  y = v + q2*(h2 - m0)  (order 3)
+ * Every expression is evaluated op by op in this order without FMA contraction, so the chain
+ *   sdmi_lincomb (data prediction, as for sdmi_dpm_step), sdmi_vq_nearest,
+ *   lincomb(c0, base, c1, h1 [, w1, h2, h1]) [, lincomb(1, v, c2 = w2, x2 = h3, x3 = h1)], lincomb(1, v, c2 = wn, m0, h1),
+ *   lincomb(p0, s, p1, m0 [, q1, h1, m0]) [, lincomb(1, v, c2 = q2, x2 = h2, x3 = m0)]
+ * gives the same bits.  x, base, h1..h3, m0, xc, y are [R][4] fp32 rows (16-byte aligned; pad channel written 0); only
+ * the first 3 channels of `out` [R][4] are read.  Refused before any launch: null pointers for the streams the two
+ * orders read or write (h1 when max(corr_order, pred_order - 1) >= 1, h2 when >= 2, h3 for corr_order 3), orders outside
+ * 0..3, more than 8192 codes, and any output (m0, xc, y, idx) that overlaps an input or another output.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* x; const float* out; const float* codebook;
+  long long* idx; float* m0;
+  int R, n_codes, target;
+  float scale, sigma, alpha;
+  const float* base; const float* h1; const float* h2; const float* h3;
+  float* xc; float* y;
+  int corr_order, pred_order;
+  float c0, c1, w1, w2, wn;
+  float p0, p1, q1, q2;
+} SdmiUnipcStepArgs;
+int sdmi_unipc_step(const SdmiUnipcStepArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Small fused elementwise kernels.
  * ------------------------------------------------------------------------------------------ */
 /* y = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div   (fp32; NULL operands skipped, x3 NULL -> c2*x2,

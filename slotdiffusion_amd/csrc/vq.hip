@@ -170,9 +170,9 @@ __device__ __forceinline__ float vq_wave_min(float v) {
 }
 
 
-// The search shared by vq_reg_kernel and dpm_step_kernel: every thread of the 256-thread workgroup calls it with the
-// (scaled) latent of row r0 + lane; `owner` (tid < VQ_LAT and a live row) gets the row's code index back, non-finite
-// rows included.  One body, so the two kernels cannot disagree on an index.
+// The search shared by vq_reg_kernel, dpm_step_kernel and unipc_step_kernel: every thread of the 256-thread workgroup
+// calls it with the (scaled) latent of row r0 + lane; `owner` (tid < VQ_LAT and a live row) gets the row's code index
+// back, non-finite rows included.  One body, so the kernels cannot disagree on an index.
 template <int NP>
 __device__ __forceinline__ int vq_reg_search(const float* __restrict__ codebook, int n_codes, float z0, float z1, float z2,
                                              float zz, bool owner) {
@@ -279,17 +279,43 @@ __global__ __launch_bounds__(256) void vq_reg_kernel(SdmiVqArgs p) {
 // search, and -- as the row's owner -- writes the quantised prediction m0 and the solver update, each as ONE 16-byte
 // vector store.  Every expression below is spelled op by op like the chain of sdmi_lincomb launches it replaces (this file
 // is compiled with -ffp-contract=off), so the bits are the chain's.
-__device__ __forceinline__ float dpm_x0(const SdmiDpmStepArgs& p, float x, float o) {
+__device__ __forceinline__ float dpm_x0(int target, float sigma, float alpha, float x, float o) {
   float eps = o;                                         // SDMI_DPM_EPS: the network predicts the noise
-  if (p.target == SDMI_DPM_X0) {                         // model_wrapper 358-361: (x - alpha * out) / sigma
-    const float t0 = 1.0f * x, t1 = (-p.alpha) * o;
-    eps = (t0 + t1) / p.sigma;
-  } else if (p.target == SDMI_DPM_V) {                   // 362-365: alpha * out + sigma * x
-    const float t0 = p.alpha * o, t1 = p.sigma * x;
+  if (target == SDMI_DPM_X0) {                           // model_wrapper 358-361: (x - alpha * out) / sigma
+    const float t0 = 1.0f * x, t1 = (-alpha) * o;
+    eps = (t0 + t1) / sigma;
+  } else if (target == SDMI_DPM_V) {                     // 362-365: alpha * out + sigma * x
+    const float t0 = alpha * o, t1 = sigma * x;
     eps = t0 + t1;
   }
-  const float t0 = 1.0f * x, t1 = (-p.sigma) * eps;      // data_prediction_fn 529: (x - sigma * eps) / alpha
-  return (t0 + t1) / p.alpha;
+  const float t0 = 1.0f * x, t1 = (-sigma) * eps;        // data_prediction_fn 529: (x - sigma * eps) / alpha
+  return (t0 + t1) / alpha;
+}
+
+// The front half both tail kernels share (P: SdmiDpmStepArgs or SdmiUnipcStepArgs, the same field names): the data
+// prediction of row r0 + lane, the search, and -- for the row's owner, the return value -- idx and the quantised
+// prediction m0, which is stored and handed back together with the row's offset.
+template <int NP, typename P>
+__device__ __forceinline__ bool dpm_predict_snap(const P& p, long long& ro, f32x4& m) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = blockIdx.x * VQ_LAT + lane;
+  ro = (long long)(r < p.R ? r : 0) * 4;
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + ro);
+  const float* o = p.out + ro;                           // (the pad channel of the network output is never read)
+  const float p0 = dpm_x0(p.target, p.sigma, p.alpha, xv[0], o[0]), p1 = dpm_x0(p.target, p.sigma, p.alpha, xv[1], o[1]),
+              p2 = dpm_x0(p.target, p.sigma, p.alpha, xv[2], o[2]);
+  const float z0 = p0 * p.scale, z1 = p1 * p.scale, z2 = p2 * p.scale;
+  const float zq0 = z0 * z0, zq1 = z1 * z1, zq2 = z2 * z2;
+  const float zz = (zq0 + zq1) + zq2;
+  const bool owner = tid < VQ_LAT && r < p.R;
+  const int bi = vq_reg_search<NP>(p.codebook, p.n_codes, z0, z1, z2, zz, owner);
+  if (!owner) return false;
+  if (p.idx) p.idx[r] = bi;
+  const float c0_ = z0 + (p.codebook[bi * 3 + 0] - z0), c1_ = z1 + (p.codebook[bi * 3 + 1] - z1),
+              c2_ = z2 + (p.codebook[bi * 3 + 2] - z2);
+  m = f32x4{c0_ / p.scale, c1_ / p.scale, c2_ / p.scale, 0.f};
+  *reinterpret_cast<f32x4*>(p.m0 + ro) = m;
+  return true;
 }
 
 __device__ __forceinline__ float dpm_update(const SdmiDpmStepArgs& p, float x, float m0, float h1, float h2) {
@@ -323,23 +349,9 @@ __device__ __forceinline__ float dpm_update(const SdmiDpmStepArgs& p, float x, f
 
 template <int NP>
 __global__ __launch_bounds__(256) void dpm_step_kernel(SdmiDpmStepArgs p) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int r = blockIdx.x * VQ_LAT + lane;
-  const long long ro = (long long)(r < p.R ? r : 0) * 4;
-  const f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + ro);
-  const float* o = p.out + ro;                           // (the pad channel of the network output is never read)
-  const float p0 = dpm_x0(p, xv[0], o[0]), p1 = dpm_x0(p, xv[1], o[1]), p2 = dpm_x0(p, xv[2], o[2]);
-  const float z0 = p0 * p.scale, z1 = p1 * p.scale, z2 = p2 * p.scale;
-  const float zq0 = z0 * z0, zq1 = z1 * z1, zq2 = z2 * z2;
-  const float zz = (zq0 + zq1) + zq2;
-  const bool owner = tid < VQ_LAT && r < p.R;
-  const int bi = vq_reg_search<NP>(p.codebook, p.n_codes, z0, z1, z2, zz, owner);
-  if (!owner) return;
-  if (p.idx) p.idx[r] = bi;
-  const float c0_ = z0 + (p.codebook[bi * 3 + 0] - z0), c1_ = z1 + (p.codebook[bi * 3 + 1] - z1),
-              c2_ = z2 + (p.codebook[bi * 3 + 2] - z2);
-  const f32x4 m = {c0_ / p.scale, c1_ / p.scale, c2_ / p.scale, 0.f};
-  *reinterpret_cast<f32x4*>(p.m0 + ro) = m;
+  long long ro;
+  f32x4 m;
+  if (!dpm_predict_snap<NP>(p, ro, m)) return;
   if (p.mode == SDMI_DPM_UPD_NONE) return;
   const f32x4 bv = *reinterpret_cast<const f32x4*>(p.base + ro);
   f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
@@ -348,6 +360,52 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(SdmiDpmStepArgs p) {
   const f32x4 y = {dpm_update(p, bv[0], m[0], h1[0], h2[0]), dpm_update(p, bv[1], m[1], h1[1], h2[1]),
                    dpm_update(p, bv[2], m[2], h1[2], h2[2]), 0.f};
   *reinterpret_cast<f32x4*>(p.y + ro) = y;
+}
+
+// ---- one function evaluation's tail of UniPC (include/sdmi.h: sdmi_unipc_step) -----------------------------------------
+// dpm_step_kernel's shape -- lane t owns row r0 + t from the load to the last store -- with a wider back half: the
+// corrector of the step just taken (from base, h1 .. h3 and the new m0) and the predictor of the next step (from the
+// corrected state, m0, h1, h2).  Six row streams in, three out, each one 16-byte vector access per row; the corrected
+// state goes from the corrector to the predictor in registers.  Spelled op by op like the sdmi_lincomb chain of sdmi.h.
+__device__ __forceinline__ float unipc_corr(const SdmiUnipcStepArgs& p, float b, float m0, float h1, float h2, float h3) {
+  const float t0 = p.c0 * b, t1 = p.c1 * h1;
+  float v = t0 + t1;                                     // c0 * base + c1 * h1
+  if (p.corr_order >= 2) { const float d = h2 - h1, t = p.w1 * d; v = v + t; }
+  if (p.corr_order == 3) { const float d = h3 - h1, t = p.w2 * d; v = v + t; }
+  const float d = m0 - h1, t = p.wn * d;
+  return v + t;
+}
+
+__device__ __forceinline__ float unipc_pred(const SdmiUnipcStepArgs& p, float b, float m0, float h1, float h2) {
+  const float t0 = p.p0 * b, t1 = p.p1 * m0;
+  float v = t0 + t1;                                     // p0 * state + p1 * m0
+  if (p.pred_order >= 2) { const float d = h1 - m0, t = p.q1 * d; v = v + t; }
+  if (p.pred_order == 3) { const float d = h2 - m0, t = p.q2 * d; v = v + t; }
+  return v;
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void unipc_step_kernel(SdmiUnipcStepArgs p) {
+  long long ro;
+  f32x4 m;
+  if (!dpm_predict_snap<NP>(p, ro, m)) return;
+  if (p.corr_order == 0 && p.pred_order == 0) return;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 st = *reinterpret_cast<const f32x4*>(p.base + ro);
+  const int need = max(p.corr_order, p.pred_order - 1);  // how many earlier predictions the two updates read
+  const f32x4 h1 = need >= 1 ? *reinterpret_cast<const f32x4*>(p.h1 + ro) : z;
+  const f32x4 h2 = need >= 2 ? *reinterpret_cast<const f32x4*>(p.h2 + ro) : z;
+  const f32x4 h3 = p.corr_order == 3 ? *reinterpret_cast<const f32x4*>(p.h3 + ro) : z;
+  if (p.corr_order > 0) {
+    st = f32x4{unipc_corr(p, st[0], m[0], h1[0], h2[0], h3[0]), unipc_corr(p, st[1], m[1], h1[1], h2[1], h3[1]),
+               unipc_corr(p, st[2], m[2], h1[2], h2[2], h3[2]), 0.f};
+    *reinterpret_cast<f32x4*>(p.xc + ro) = st;
+  }
+  if (p.pred_order > 0) {
+    const f32x4 y = {unipc_pred(p, st[0], m[0], h1[0], h2[0]), unipc_pred(p, st[1], m[1], h1[1], h2[1]),
+                     unipc_pred(p, st[2], m[2], h1[2], h2[2]), 0.f};
+    *reinterpret_cast<f32x4*>(p.y + ro) = y;
+  }
 }
 
 }  // namespace
@@ -384,4 +442,43 @@ extern "C" int sdmi_dpm_step(const SdmiDpmStepArgs* a, void* stream) {
   else if (a->n_codes <= 4 * 128 * 8) hipLaunchKernelGGL(dpm_step_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, *a);
   else hipLaunchKernelGGL(dpm_step_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, *a);
   return sdmi_check_launch("dpm_step");
+}
+
+// byte ranges [a, a + na) and [b, b + nb) intersect (a null pointer has no range)
+static bool spans_overlap(const void* a, long long na, const void* b, long long nb) {
+  const char *x = (const char*)a, *y = (const char*)b;
+  return a && b && x < y + nb && y < x + na;
+}
+
+extern "C" int sdmi_unipc_step(const SdmiUnipcStepArgs* a, void* stream) {
+  SDMI_REQUIRE(a && a->x && a->out && a->codebook && a->m0, "null pointer");
+  SDMI_REQUIRE(a->R >= 1 && a->n_codes >= 1 && a->n_codes <= 4 * 128 * 16, "bad shape (codebooks up to 8192 codes)");
+  SDMI_REQUIRE(a->target >= SDMI_DPM_EPS && a->target <= SDMI_DPM_V, "unknown prediction target");
+  SDMI_REQUIRE(a->corr_order >= 0 && a->corr_order <= 3 && a->pred_order >= 0 && a->pred_order <= 3,
+               "corrector / predictor order outside 0..3");
+  const int need = a->corr_order > a->pred_order - 1 ? a->corr_order : a->pred_order - 1;
+  SDMI_REQUIRE((a->corr_order == 0 && a->pred_order == 0) || a->base, "update without base state");
+  SDMI_REQUIRE(a->corr_order == 0 || a->xc, "corrector without destination");
+  SDMI_REQUIRE(a->pred_order == 0 || a->y, "predictor without destination");
+  SDMI_REQUIRE((need < 1 || a->h1) && (need < 2 || a->h2) && (a->corr_order < 3 || a->h3),
+               "orders need more earlier predictions than given");
+  SDMI_REQUIRE(a->scale != 0.f && a->alpha != 0.f && (a->target != SDMI_DPM_X0 || a->sigma != 0.f), "zero divisor");
+  {
+    const long long row = (long long)a->R * 16;
+    const void* ins[7] = {a->x, a->out, a->base, a->h1, a->h2, a->h3, a->codebook};
+    const long long nin[7] = {row, row, row, row, row, row, (long long)a->n_codes * 12};
+    const void* outs[4] = {a->m0, a->corr_order ? a->xc : nullptr, a->pred_order ? a->y : nullptr, a->idx};
+    const long long nout[4] = {row, row, row, (long long)a->R * 8};
+    for (int o = 0; o < 4; ++o) {
+      for (int i = 0; i < 7; ++i)
+        SDMI_REQUIRE(!spans_overlap(outs[o], nout[o], ins[i], nin[i]), "an output aliases an input");
+      for (int j = o + 1; j < 4; ++j)
+        SDMI_REQUIRE(!spans_overlap(outs[o], nout[o], outs[j], nout[j]), "two outputs alias");
+    }
+  }
+  const dim3 grid((a->R + VQ_LAT - 1) / VQ_LAT);
+  if (a->n_codes <= 4 * 128 * 4) hipLaunchKernelGGL(unipc_step_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  else if (a->n_codes <= 4 * 128 * 8) hipLaunchKernelGGL(unipc_step_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(unipc_step_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  return sdmi_check_launch("unipc_step");
 }

@@ -17,13 +17,14 @@ import torch
 
 
 class DiscreteSchedule:
-    """log(alpha_t) table on t_i = (i+1)/N with piecewise-linear interpolation (fp32)."""
+    """log(alpha_t) table on t_i = (i+1)/N with piecewise-linear interpolation (fp32; unipc.py asks for float64)."""
 
-    def __init__(self, betas):
-        betas = torch.as_tensor(betas, dtype=torch.float32).cpu()
-        self.log_alpha = (0.5 * torch.log(1 - betas).cumsum(dim=0)).float()
+    def __init__(self, betas, dtype=torch.float32):
+        betas = torch.as_tensor(betas, dtype=dtype).cpu()
+        self.dtype = dtype
+        self.log_alpha = (0.5 * torch.log(1 - betas).cumsum(dim=0)).to(dtype)
         self.N = int(self.log_alpha.numel())
-        self.t_array = torch.linspace(0., 1., self.N + 1)[1:].float()
+        self.t_array = torch.linspace(0., 1., self.N + 1, dtype=dtype)[1:]
         self.T = 1.0
 
     @staticmethod
@@ -50,7 +51,7 @@ class DiscreteSchedule:
         return lm - 0.5 * torch.log(1. - torch.exp(2. * lm))
 
     def inverse_lambda(self, lamb):
-        la = -0.5 * torch.logaddexp(torch.zeros((1,)), -2. * lamb)
+        la = -0.5 * torch.logaddexp(torch.zeros((1,), dtype=self.dtype), -2. * lamb)
         return self._interp(la.reshape(-1), torch.flip(self.log_alpha, [0]),
                             torch.flip(self.t_array, [0]))
 
@@ -99,13 +100,14 @@ def check_options(method='singlestep', order=3, skip_type='time_uniform', solver
 
 def time_steps(ns, skip_type, t_T, t_0, N):
     """get_time_steps (dpm_solver.py:545-572): N + 1 times from t_T down to t_0."""
+    dt = ns.dtype
     if skip_type == 'logSNR':
-        lam_T, lam_0 = ns.lam(torch.tensor(t_T)), ns.lam(torch.tensor(t_0))
-        return ns.inverse_lambda(torch.linspace(lam_T.item(), lam_0.item(), N + 1))
+        lam_T, lam_0 = ns.lam(torch.tensor(t_T, dtype=dt)), ns.lam(torch.tensor(t_0, dtype=dt))
+        return ns.inverse_lambda(torch.linspace(lam_T.item(), lam_0.item(), N + 1, dtype=dt))
     if skip_type == 'time_uniform':
-        return torch.linspace(t_T, t_0, N + 1)
+        return torch.linspace(t_T, t_0, N + 1, dtype=dt)
     if skip_type == 'time_quadratic':
-        return torch.linspace(t_T ** (1. / 2), t_0 ** (1. / 2), N + 1).pow(2)
+        return torch.linspace(t_T ** (1. / 2), t_0 ** (1. / 2), N + 1, dtype=dt).pow(2)
     raise ValueError(f'skip_type={skip_type!r}: must be one of {SKIP_TYPES}')
 
 

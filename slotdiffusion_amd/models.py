@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import dpm, engine, kern, ops, spec
+from . import dpm, engine, kern, ops, spec, unipc
 from .module import FlatModule, _Node
 
 _DTYPES = {'fp32': torch.float32, 'float32': torch.float32, 'bf16': torch.bfloat16,
@@ -218,9 +218,13 @@ class LDM(_Owned):
     def generate_imgs(self, cond, batch_size=16, ret_intermed=False, verbose=False,
                       use_ddim=False, use_dpm=True, x_T=None, same_noise=False, dpm_steps=None, dpm_order=3,
                       dpm_method='singlestep', dpm_skip_type='time_uniform', dpm_t_start=None, dpm_t_end=None,
-                      dpm_denoise_to_zero=False, dpm_lower_order_final=True, **kwargs):
+                      dpm_denoise_to_zero=False, dpm_lower_order_final=True, use_unipc=False, unipc_steps=None,
+                      unipc_order=3, unipc_variant='bh2', unipc_skip_type='time_uniform', unipc_t_start=None,
+                      unipc_t_end=None, unipc_lower_order_final=True, unipc_corrector=True, unipc_denoise_to_zero=False,
+                      **kwargs):
         """cond_ddpm.py:134-212: DPM-Solver++ (use_dpm, takes precedence), DDIM (use_ddim) or the
-        T-step ancestral sampler.  Returns latents [B,3,h,w] (NCHW fp32).
+        T-step ancestral sampler; use_unipc (not in the reference) takes precedence over all three.  Returns latents
+        [B,3,h,w] (NCHW fp32).
 
         The dpm_* keywords are DPM_Solver.sample's (dpm_solver.py:1190-1345): steps (None: max(20, T // 50) as the
         reference's caller passes), order 1-3, method 'singlestep' | 'singlestep_fixed' | 'multistep', skip_type
@@ -229,9 +233,23 @@ class LDM(_Owned):
         argument: dpm_method='adaptive', dpm_solver_type='taylor', dpm_algorithm_type='dpmsolver',
         dpm_correcting_x0_fn (dynamic thresholding), guidance_scale != 1.  With ret_intermed the second result is the
         reference's `intermediates`: one state per outer step (singlestep), the initial state and one per step
-        (multistep), then the denoise_to_zero state when asked."""
+        (multistep), then the denoise_to_zero state when asked.
+
+        The unipc_* keywords are unipc.build_plan's: steps (None: the rule of dpm_steps), order 1-3, variant 'bh1' |
+        'bh2', skip_type / t_start / t_end as above, lower_order_final, corrector (False: the predictor UniP alone),
+        denoise_to_zero.  Refused by name as well: unipc_variant='vary_coeff', unipc_method other than 'multistep', and
+        through unipc_solver_type / unipc_algorithm_type / unipc_correcting_x0_fn / guidance_scale what the DPM path
+        refuses.  With ret_intermed: the initial state, the carried state after every step, then the denoise_to_zero
+        state when asked."""
         r = self.root
-        if use_dpm:
+        if use_unipc:
+            unipc.check_options(order=unipc_order, variant=unipc_variant, skip_type=unipc_skip_type, steps=unipc_steps,
+                                method=kwargs.get('unipc_method', 'multistep'),
+                                solver_type=kwargs.get('unipc_solver_type', 'dpmsolver'),
+                                algorithm_type=kwargs.get('unipc_algorithm_type', 'dpmsolver++'),
+                                correcting_x0_fn=kwargs.get('unipc_correcting_x0_fn'),
+                                guidance_scale=kwargs.get('guidance_scale', 1.))
+        elif use_dpm:
             dpm.check_options(method=dpm_method, order=dpm_order, skip_type=dpm_skip_type,
                               solver_type=kwargs.get('dpm_solver_type', 'dpmsolver'),
                               algorithm_type=kwargs.get('dpm_algorithm_type', 'dpmsolver++'),
@@ -247,7 +265,12 @@ class LDM(_Owned):
             else:
                 x_T = torch.randn(batch_size, 3, h, w, device=cond.device)
         x = ops.nchw_to_nhwc(x_T, torch.float32, 4)
-        if use_dpm:            # cond_ddpm.py:155-178 (takes precedence, as in the reference)
+        if use_unipc:
+            x, inter = r._unipc_sample(x, cond, ret_intermed, steps=unipc_steps, order=unipc_order, variant=unipc_variant,
+                                       skip_type=unipc_skip_type, t_start=unipc_t_start, t_end=unipc_t_end,
+                                       lower_order_final=unipc_lower_order_final, corrector=unipc_corrector,
+                                       denoise_to_zero=unipc_denoise_to_zero)
+        elif use_dpm:          # cond_ddpm.py:155-178 (takes precedence, as in the reference)
             x, inter = r._dpm_sample(x, cond, ret_intermed, steps=dpm_steps, order=dpm_order, method=dpm_method,
                                      skip_type=dpm_skip_type, t_start=dpm_t_start, t_end=dpm_t_end,
                                      denoise_to_zero=dpm_denoise_to_zero, lower_order_final=dpm_lower_order_final)
@@ -405,7 +428,7 @@ class SADiffusion(SlotModelBase):
         self.dm_decoder.vae._bind(self)
         self._bank = None
         self._unet = None
-        self._plans = {}           # solver configuration (dpm.plan_key) -> (plan, model times on the device, program)
+        self._plans = {}           # dpm.plan_key / unipc.plan_key -> (plan, model times on the device, program)
         self._Kinf = self._Kgrad = None
         self.step_seed = None      # device word mixed into dropout seeds (see optim.GraphedTrainStep)
         self.eval_seed = None      # its no_grad / validation counterpart (LDM._draw_tn)
@@ -449,12 +472,17 @@ class SADiffusion(SlotModelBase):
         dflt = dpm.plan_key(steps)
         default = cfg[:6] + cfg[7:] == dflt[:6] + dflt[7:]          # (lower_order_final means nothing to singlestep)
         loop = self._dpm_loop if default else self._dpm_family_loop
+        return self._sample_graphed(loop, lambda: self._dpm_prepare(cfg, x.device), cfg, x, cond, ret_intermed)
+
+    def _sample_graphed(self, loop, prepare, cfg, x, cond, ret_intermed):
+        """loop(x, cond, prepare(), ret_intermed) -> (x_0, intermediates), eagerly -- or, with use_graph and no
+        intermediates asked, from the HIP graph captured once per (batch, solver configuration cfg, condition shape)."""
         if ret_intermed or not self.use_graph:
-            return loop(x, cond, self._dpm_prepare(cfg, x.device), ret_intermed)
+            return loop(x, cond, prepare(), ret_intermed)
         key = (x.shape[0], cfg, tuple(cond.shape))
         g = self._graph_cache.get(key)
         if g is None:
-            prep = self._dpm_prepare(cfg, x.device)
+            prep = prepare()
             sx, sc = torch.empty_like(x), torch.empty_like(cond)
             sx.copy_(x)
             sc.copy_(cond)
@@ -472,6 +500,63 @@ class SADiffusion(SlotModelBase):
         sc.copy_(cond)
         graph.replay()
         return out, []
+
+    def _unipc_sample(self, x, cond, ret_intermed=False, steps=None, **solver):
+        """x [B,h,w,4] fp32 state at t_start -> x_0 with UniPC (unipc.py).  `solver`: the keywords of unipc.build_plan.
+        One HIP graph per batch size, condition shape and full UniPC configuration; unipc.plan_key starts with a tag no
+        dpm.plan_key has, so the plan and graph caches never hand a DPM entry to UniPC or the reverse."""
+        steps = steps or max(20, self.dm_decoder.num_timesteps // 50)
+        cfg = unipc.plan_key(steps, **solver)
+        return self._sample_graphed(self._unipc_loop, lambda: self._unipc_prepare(cfg, x.device), cfg, x, cond,
+                                    ret_intermed)
+
+    @staticmethod
+    def unipc_cache_key(batch, cond_shape, steps=20, **solver):
+        """Key of the HIP-graph cache entry of one UniPC sampler call (never equal to a dpm_cache_key)."""
+        return (batch, unipc.plan_key(steps, **solver), tuple(cond_shape))
+
+    def _unipc_prepare(self, cfg, device):
+        """cfg (unipc.plan_key) -> (plan, model times of its evaluations on the device, flat program)."""
+        ent = self._plans.get((cfg, device))
+        if ent is None:
+            betas = self.dm_decoder.betas.detach().double().cpu()
+            names = ('steps', 'order', 'variant', 'skip_type', 't_start', 't_end', 'lower_order_final', 'corrector',
+                     'denoise_to_zero')
+            plan = unipc.build_plan(betas, **dict(zip(names, cfg[1:])))
+            tin = torch.tensor(unipc.plan_t_inputs(plan), dtype=torch.float32, device=device)
+            ent = self._plans[(cfg, device)] = (plan, tin, unipc.program(plan))
+        return ent
+
+    def _unipc_loop(self, x, cond, prep, ret_intermed):
+        """Per function evaluation the UNet and ONE sdmi_unipc_step launch (data prediction for the model's target, VQ,
+        the corrector of the step just taken, the predictor of the next), driven by unipc.run_program.  The solver
+        state stays fp32 in every compute dtype.  The predictions rotate through four buffers (the newest and the three
+        the third-order corrector reads), the corrected and the predicted state through two each; with ret_intermed the
+        corrected states are returned, so each gets a buffer of its own."""
+        plan, tin, prog = prep
+        u = self.unet()
+        Kp = self.K()
+        ctx_kv = u.context_kv(Kp, self._ctx(cond))
+        rv_all = u.time_rowvecs(Kp, tin)
+        B = x.shape[0]
+        code = self.bank().f(self.vq_key)
+        target = self.dm_decoder.pred_target
+        hist = [torch.empty_like(x) for _ in range(4)]
+        xcs = [torch.empty_like(x) for _ in range(2)]
+        ys = [torch.empty_like(x) for _ in range(2)]
+        nfe = [0]
+
+        def tail(xe, rec, base, h1, h2, h3):
+            n = nfe[0]
+            nfe[0] += 1
+            rv = rv_all[n:n + 1].expand(B, -1)
+            out = u.forward(Kp, self._unet_in(xe), rv, ctx_kv, zero_pad=False)     # (the pad channel is never read)
+            return ops.unipc_step(xe, out, code, rec, scale=self.z_scale, target=target, base=base, h1=h1, h2=h2, h3=h3,
+                                  m0=hist[n % 4], xc=None if ret_intermed else xcs[n % 2],
+                                  y=None if ret_intermed else ys[n % 2])[:3]
+
+        x, inter = unipc.run_program(prog, x, tail)
+        return x, (inter if ret_intermed else [])
 
     def _ddim_sample(self, x, cond, steps, eta=0., ret_intermed=False, log_every_t=100):
         """DDIMSampler._sample_x0_from_noise (ddim.py:128-218) for eps-prediction with the VQ

@@ -504,6 +504,39 @@ def dpm_step(x, out, codebook, e, *, scale=1.0, target='eps', upd=None, base=Non
     return m0, y, idx
 
 
+def unipc_step(x, out, codebook, rec, *, scale=1.0, target='eps', base=None, h1=None, h2=None, h3=None, m0=None,
+               xc=None, y=None, want_idx=False):
+    """One UniPC function evaluation's tail in one launch (sdmi.h: sdmi_unipc_step): data prediction of state x [..., 4]
+    from the network output `out` at the record's evaluation (rec: one entry of unipc.program), nearest code, the
+    corrector of the step just taken (rec['corr']) from `base` and the earlier predictions h1..h3, and the predictor of
+    the next step (rec['pred']).  m0 / xc / y: optional destinations (the sampler rotates its buffers).
+    -> (m0, xc or None, y or None, idx or None)."""
+    _need_gpu(x, out, codebook)
+    assert x.shape[-1] == 4 and out.shape == x.shape and codebook.shape[1] == 3
+    corr, pred = rec['corr'], rec['pred']
+    ts = [t for t in (x, out, base, h1, h2, h3, m0, xc, y) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape for t in ts)
+    m0 = torch.empty_like(x) if m0 is None else m0
+    idx = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device) if want_idx else None
+    kw = {}
+    if corr is not None:
+        xc = torch.empty_like(x) if xc is None else xc
+        kw.update(corr_order=corr['order'], xc=_p(xc), **{k: float(corr[k]) for k in ('c0', 'c1', 'w1', 'w2', 'wn')})
+    else:
+        xc = None
+    if pred is not None:
+        y = torch.empty_like(x) if y is None else y
+        kw.update(pred_order=pred['order'], y=_p(y), p0=float(pred['c0']), p1=float(pred['c1']), q1=float(pred['q1']),
+                  q2=float(pred['q2']))
+    else:
+        y = None
+    call('sdmi_unipc_step', _stream(), x=_p(x), out=_p(out), codebook=_p(codebook), idx=_p(idx), m0=_p(m0),
+         R=x.numel() // 4, n_codes=codebook.shape[0], target=_DPM_TARGET[target], scale=scale,
+         sigma=float(rec['e']['sigma']), alpha=float(rec['e']['alpha']), base=_p(base), h1=_p(h1), h2=_p(h2), h3=_p(h3),
+         **kw)
+    return m0, xc, y, idx
+
+
 def lincomb(c0=0., x0=None, c1=0., x1=None, c2=0., x2=None, x3=None, div=0., out=None):
     """out = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div  (fp32 tensors; see sdmi.h)."""
     ref = x0 if x0 is not None else (x1 if x1 is not None else x2)
