@@ -340,6 +340,13 @@ def plan_key(steps=20, order=3, method='singlestep', skip_type='time_uniform', t
             bool(lower_order_final), bool(denoise_to_zero))
 
 
+def plan_from_key(betas, key):
+    """build_plan of the configuration a plan_key names (the key's order is spelled here and in plan_key alone)."""
+    steps, order, method, skip_type, t_start, t_end, lower_order_final, denoise_to_zero = key
+    return build_plan(betas, steps=steps, order=order, method=method, skip_type=skip_type, t_start=t_start, t_end=t_end,
+                      lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero)
+
+
 def plan_t_inputs(plan):
     tin = [e['t_input'] for st in plan['steps'] for e in st['evals']]
     return tin + ([plan['denoise']['t_input']] if 'denoise' in plan else [])

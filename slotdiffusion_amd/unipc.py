@@ -199,5 +199,14 @@ def plan_key(steps=20, order=3, variant='bh2', skip_type='time_uniform', t_start
             bool(lower_order_final), bool(corrector), bool(denoise_to_zero))
 
 
+def plan_from_key(betas, key):
+    """build_plan of the configuration a plan_key names (the key's order is spelled here and in plan_key alone)."""
+    tag, steps, order, variant, skip_type, t_start, t_end, lower_order_final, corrector, denoise_to_zero = key
+    assert tag == 'unipc'
+    return build_plan(betas, steps=steps, order=order, variant=variant, skip_type=skip_type, t_start=t_start,
+                      t_end=t_end, lower_order_final=lower_order_final, corrector=corrector,
+                      denoise_to_zero=denoise_to_zero)
+
+
 def plan_t_inputs(plan):
     return [e['t_input'] for e in plan['evals']] + ([plan['denoise']['t_input']] if 'denoise' in plan else [])

@@ -20,6 +20,14 @@ CONFIGS = [
     ('ss3_12_t06', dict(method='singlestep', order=3, steps=12, t_start=0.6)),
 ]
 BAR = 1e-4                # the project's fp32 bar on solver states
+# (configuration, number of intermediates) and the configurations whose cache keys must differ from the default's
+COUNTS = ((dict(method='multistep', order=2, steps=10), 11),
+          (dict(method='singlestep', order=3, steps=20), 7),
+          (dict(method='singlestep_fixed', order=2, steps=10, denoise_to_zero=True), 6),
+          (dict(method='multistep', order=3, steps=8, denoise_to_zero=True), 10))
+KEYED = [dict(steps=10), dict(order=2), dict(method='multistep'), dict(method='singlestep_fixed'),
+         dict(skip_type='logSNR'), dict(skip_type='time_quadratic'), dict(t_start=0.6), dict(t_end=1e-4),
+         dict(denoise_to_zero=True), dict(method='multistep', lower_order_final=False)]
 
 
 def betas():
@@ -106,16 +114,24 @@ def test_program_reproduces_the_reference_toy_trajectory(tag, kw):
 
 def test_intermediates_count_per_method():
     b = betas()
-    for kw, n in ((dict(method='multistep', order=2, steps=10), 11),
-                  (dict(method='singlestep', order=3, steps=20), 7),
-                  (dict(method='singlestep_fixed', order=2, steps=10, denoise_to_zero=True), 6),
-                  (dict(method='multistep', order=3, steps=8, denoise_to_zero=True), 10)):
+    for kw, n in COUNTS:
         prog = dpm.program(dpm.build_plan(b, **kw))
         z = torch.zeros(1)
         _, inter = dpm.run_program(prog, z, lambda x, e, u, base, h1, h2: (z, z if u is not None else None),
                                    emit_initial=kw['method'] == 'multistep')
         assert len(inter) == n, (kw, len(inter))
         assert len(prog) == kw['steps'] + int(kw.get('denoise_to_zero', False))
+
+
+def test_plan_from_key_builds_the_plan_of_the_keywords():
+    """plan_key -> plan_from_key gives build_plan's program and model times for every configuration of this file: the
+    key's order and the keyword names agree."""
+    b = betas()
+    for kw in [{}] + [kw for _, kw in CONFIGS] + [kw for kw, _ in COUNTS] + KEYED:
+        got, want = dpm.plan_from_key(b, dpm.plan_key(**kw)), dpm.build_plan(b, **kw)
+        assert dpm.program(got) == dpm.program(want), kw
+        assert dpm.plan_t_inputs(got) == dpm.plan_t_inputs(want), kw
+        assert got.get('method') == want.get('method'), kw
 
 
 def test_refused_options_raise_value_error_naming_the_argument():
@@ -163,10 +179,7 @@ def test_distinct_configuration_distinct_cache_key():
     key = SADiffusion.dpm_cache_key
     base = key(64, (64, 7, 192))
     assert base == key(64, (64, 7, 192), steps=20, order=3, method='singlestep')
-    others = [dict(steps=10), dict(order=2), dict(method='multistep'), dict(method='singlestep_fixed'),
-              dict(skip_type='logSNR'), dict(skip_type='time_quadratic'), dict(t_start=0.6), dict(t_end=1e-4),
-              dict(denoise_to_zero=True), dict(method='multistep', lower_order_final=False)]
-    keys = [key(64, (64, 7, 192), **kw) for kw in others] + [key(32, (32, 7, 192)), key(64, (64, 11, 192))]
+    keys = [key(64, (64, 7, 192), **kw) for kw in KEYED] + [key(32, (32, 7, 192)), key(64, (64, 11, 192))]
     assert len(set(keys + [base])) == len(keys) + 1
     assert dpm.plan_key(t_start=0.6) == dpm.plan_key(t_start=torch.tensor(0.6, dtype=torch.float64).item())
     hash(base)

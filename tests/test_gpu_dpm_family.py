@@ -158,35 +158,59 @@ def test_reference_configurations_fp32(tag, kw):
     assert torch.equal(x2, x)
 
 
-def test_default_arguments_keep_the_parent_sampler():
-    """Omitting the keywords, or spelling the defaults, runs the parent's loop and launch list (no sdmi_dpm_step)."""
-    from slotdiffusion_amd import _lib
+@pytest.mark.parametrize('target', TARGETS)
+def test_default_equals_the_parent_launch_chain(target):
+    """The default (omitting the keywords, or spelling them) runs one sdmi_dpm_step per evaluation, and its final latent
+    and every intermediate state are bit-identical to the launches it ran before the fused tail: the same program with
+    sdmi_lincomb / sdmi_vq_nearest (_chain) behind the same UNet evaluator."""
+    from slotdiffusion_amd import _lib, ops
     m, G, _ = ctx()
     dm = m.dm_decoder
+    cond, x_T = G['slots'].cuda(), G['x_T'].cuda()
+    assert not m.use_graph                               # (the graph and plan caches do not key on the target)
     calls = []
     real = _lib._call
 
     def spy(fname, stream, **kw):
         calls.append(fname)
         return real(fname, stream, **kw)
+    x_in = ops.nchw_to_nhwc(x_T, torch.float32, 4)
+    m._evaluator(cond, [0.], zero_pad=False)(x_in)       # one evaluation: the lazy weight preparation is no launch list
+    was = dm.pred_target
+    dm.pred_target = target
     _lib._call = spy
     try:
-        a = dm.generate_imgs(cond=G['slots'].cuda(), batch_size=2, x_T=G['x_T'].cuda())
+        a = dm.generate_imgs(cond=cond, batch_size=2, x_T=x_T)
         n_default = list(calls)
         del calls[:]
-        b = dm.generate_imgs(cond=G['slots'].cuda(), batch_size=2, x_T=G['x_T'].cuda(), dpm_steps=20, dpm_order=3,
-                             dpm_method='singlestep', dpm_skip_type='time_uniform')
+        b = dm.generate_imgs(cond=cond, batch_size=2, x_T=x_T, dpm_steps=20, dpm_order=3, dpm_method='singlestep',
+                             dpm_skip_type='time_uniform')
         n_spelled = list(calls)
         del calls[:]
-        dm.generate_imgs(cond=G['slots'].cuda(), batch_size=2, x_T=G['x_T'].cuda(), dpm_method='multistep', dpm_order=2,
-                         dpm_steps=10)
+        dm.generate_imgs(cond=cond, batch_size=2, x_T=x_T, dpm_method='multistep', dpm_order=2, dpm_steps=10)
         n_multi = list(calls)
+        _lib._call = real
+        x, inter = m._dpm_sample(x_in, cond, ret_intermed=True)
+        plan = dpm.build_plan(dm.betas.detach().cpu())
+        ev = m._evaluator(cond, dpm.plan_t_inputs(plan), zero_pad=False)
+
+        def tail(xc, e, upd, base, h1, h2):
+            return _chain(ops, xc, ev(xc), ev.code, e, m.z_scale, target, upd, base, h1, h2)[1:]
+        x_c, inter_c = dpm.run_program(dpm.program(plan), x_in, tail)
+        torch.cuda.synchronize()
     finally:
         _lib._call = real
+        dm.pred_target = was
     assert torch.equal(a, b) and n_default == n_spelled
-    assert 'sdmi_dpm_step' not in n_default and n_default.count('sdmi_vq_nearest') == 20
-    assert float((a.cpu() - G['dpm_final']).abs().max()) <= BAR
+    assert n_default.count('sdmi_dpm_step') == 20 and 'sdmi_vq_nearest' not in n_default
     assert n_multi.count('sdmi_dpm_step') == 10 and 'sdmi_vq_nearest' not in n_multi
+    assert ev.n == 20 and len(inter) == len(inter_c) == 7          # one state per outer step, no initial state
+    assert _same(ops.nhwc_to_nchw(x, 3), a)                      # with and without intermediates: the same latent
+    for got, want in zip([x] + inter, [x_c] + inter_c):
+        assert _same(got[..., :3], want[..., :3])
+        assert (got[..., 3] == 0).all()
+    if target == 'eps':
+        assert float((a.cpu() - G['dpm_final']).abs().max()) <= BAR
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])

@@ -13,6 +13,13 @@ from slotdiffusion_amd import _lib, dpm, module, unipc
 
 MU, S = 0.7, 0.5
 F64 = torch.float64
+# the configurations whose cache keys must differ from the default's, and the other plans the tests below build
+KEYED = [dict(steps=10), dict(order=2), dict(variant='bh1'), dict(skip_type='logSNR'),
+         dict(skip_type='time_quadratic'), dict(t_start=0.6), dict(t_end=1e-4), dict(lower_order_final=False),
+         dict(corrector=False), dict(denoise_to_zero=True)]
+BUILT = [dict(steps=10, order=3), dict(steps=10, order=3, denoise_to_zero=True), dict(steps=10, order=3, corrector=False),
+         dict(steps=5, t_start=0.6, t_end=0.01), dict(steps=20, order=3, variant='bh2', skip_type='logSNR'),
+         dict(steps=40, order=3, variant='bh2', skip_type='logSNR')]
 
 
 def betas64():
@@ -125,6 +132,16 @@ def test_order_and_corrector_sequences():
     assert float(t06['outer'][0]) == 0.6 and float(t06['outer'][-1]) == 0.01 and t06['outer'].dtype == F64
 
 
+def test_plan_from_key_builds_the_plan_of_the_keywords():
+    """plan_key -> plan_from_key gives build_plan's program and model times for every configuration of this file: the
+    key's order and the keyword names agree."""
+    b = betas64()
+    for kw in [{}] + KEYED + BUILT:
+        got, want = unipc.plan_from_key(b, unipc.plan_key(**kw)), unipc.build_plan(b, **kw)
+        assert unipc.program(got) == unipc.program(want), kw
+        assert unipc.plan_t_inputs(got) == unipc.plan_t_inputs(want), kw
+
+
 @pytest.mark.parametrize('nfe', [20, 40])
 def test_trajectory_error_is_below_the_multistep_solvers(nfe):
     """logSNR grid from t = 1 to 1 / T on the toy: UniPC (order 3, bh2, corrector) ends closer to the exact solution than
@@ -197,10 +214,7 @@ def test_cache_keys_are_distinct_across_unipc_and_dpm_configurations():
     shape = (64, 7, 192)
     base = ukey(64, shape)
     assert base == ukey(64, shape, steps=20, order=3, variant='bh2', corrector=True)
-    others = [dict(steps=10), dict(order=2), dict(variant='bh1'), dict(skip_type='logSNR'),
-              dict(skip_type='time_quadratic'), dict(t_start=0.6), dict(t_end=1e-4), dict(lower_order_final=False),
-              dict(corrector=False), dict(denoise_to_zero=True)]
-    ukeys = [base] + [ukey(64, shape, **kw) for kw in others] + [ukey(32, (32, 7, 192)), ukey(64, (64, 11, 192))]
+    ukeys = [base] + [ukey(64, shape, **kw) for kw in KEYED] + [ukey(32, (32, 7, 192)), ukey(64, (64, 11, 192))]
     dkeys = [dkey(64, shape), dkey(64, shape, method='multistep'), dkey(64, shape, method='multistep', steps=10),
              dkey(64, shape, method='multistep', skip_type='logSNR'), dkey(64, shape, denoise_to_zero=True)]
     assert len(set(ukeys + dkeys)) == len(ukeys) + len(dkeys)
