@@ -579,6 +579,53 @@ typedef struct {
 int sdmi_rollout_layer(const SdmiRolloutLayerArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Physion VQA readout (PhysionReadout.forward + calc_train_loss, vp_vqa/models/readout.py:56-87): per frame, linear1 on
+ * every slot pair [s_i | s_j] (i < j, itertools.combinations order), a symmetric aggregate over the pairs, linear2, then
+ * the max over time and (optionally) the BCE-with-logits loss.  linear1([s_i | s_j]) = W_a s_i + W_b s_j + b1 with
+ * W_a = W1[:, :C], W_b = W1[:, C:], so U = S W_a^T and V = S W_b^T are computed once per slot ROW on the matrix cores
+ * and the [B, T, P, 2C] pair tensor never exists; the aggregate runs on U and V in registers:
+ *   max: max_{i<j}(U_i + V_j) + b1 (running prefix max of U);  sum: sum_i (N-1-i) U_i + sum_j j V_j + P b1;  mean: sum / P.
+ * TWO launches: tiles of whole frames -> frame_logits; a one-workgroup finisher -> logits, t_star, loss, dlogit.
+ *   slots [B][T][N][C] contiguous, x_dtype fp32 or bf16, 16-byte aligned.  Operands are rounded to op_dtype on load;
+ *     bf16 operands: U, V and the aggregate are fp32 (v_mfma_f32_32x32x16_bf16).  fp32 operands (the parity configuration):
+ *     v_mfma_f32_32x32x2_f32 sums 8 k at a time in fp32, the chunks and the aggregate are carried in fp64 (a 256-term
+ *     fp32 dot product alone is 3e-7 of the logit's magnitude off: 3e-5 at the sum aggregate of 16 slots).  In both, the
+ *     sum of linear2's F products is carried in fp64 and rounded to fp32 once; the time max and the loss are fp32.
+ *   w1p: linear1.weight [F][2C] in op_dtype, packed per 32-feature chunk fc and k step into MFMA B fragments
+ *     (python: kern.readout_pack_index):  bf16  w1p[(((fc C/16 + ks) 2 + h) 64 + l) 8 + e] = W1[32 fc + l%32][h C + 16 ks + 8 (l/32) + e]
+ *                                         fp32  w1p[(((fc C/8 + kg) 2 + h) 64 + l) 4 + j] = W1[32 fc + l%32][h C + 8 kg + 4 (l/32) + j]
+ *   b1 [F], w2 [F], b2 [1] fp32.  agg: 0 sum, 1 mean, 2 max.
+ *   frame_logits [B][T] (b2 included), logits [B] = max_t, t_star [B] int32 (lowest t on ties).
+ *   label (optional, [B] fp32): loss [1] = loss_weight mean_b (max(x,0) - x y + log1p(exp(-|x|))),
+ *     dlogit [B] = loss_weight (sigmoid(x) - y) / B.
+ *   phase: 0 = both launches, 1 = frame logits only, 2 = finisher only (reads frame_logits).
+ *   2 <= N <= 16; C, F multiples of 32 up to 256; T, B >= 1.  No atomics: bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+enum { SDMI_AGG_SUM = 0, SDMI_AGG_MEAN = 1, SDMI_AGG_MAX = 2 };
+typedef struct {
+  const void* slots; const void* w1p; const float* b1; const float* w2; const float* b2;
+  const float* label;
+  float* frame_logits; float* logits; int* t_star; float* loss; float* dlogit;
+  int B, T, N, C, F, agg, x_dtype, op_dtype, phase;
+  float loss_weight;
+} SdmiReadoutFwdArgs;
+int sdmi_readout_fwd(const SdmiReadoutFwdArgs* a, void* stream);
+/* Backward of the readout in ONE launch.  Only the frame t_star[b] of every sample carries gradient: one wave per
+ * feature f walks b = 0 .. B-1 in order, recomputes U, V of that frame for f in fp32 FMA (operands rounded to op_dtype
+ * as in the forward), re-derives the aggregate (max: the winning pair (i*, j*), ties to the first pair in combinations
+ * order; sum / mean: the fixed weights) and accumulates, with g = gscale[0] dlogit[b] (gscale: optional device scalar)
+ *   dW1[f] (+)= g w2[f] [s_i* | s_j*],  db1[f] (+)= g w2[f] (x P for sum),  dW2[f] (+)= g m[b][f],  db2 (+)= sum_b g.
+ * dw1 [F][2C], db1 [F], dw2 [F], db2 [1] fp32; accumulate != 0 adds to them (the gradient arena), 0 overwrites.
+ * Nothing of size B T F is read: slots, t_star and dlogit are enough.  No gradient reaches slots. */
+typedef struct {
+  const void* slots; const void* w1p; const float* b1; const float* w2;
+  const int* t_star; const float* dlogit; const float* gscale;
+  float* dw1; float* db1; float* dw2; float* db2;
+  int B, T, N, C, F, agg, x_dtype, op_dtype, accumulate;
+} SdmiReadoutBwdArgs;
+int sdmi_readout_bwd(const SdmiReadoutBwdArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training twin of the fused SpatialTransformer block (bf16): the forward pass of
  * SpatialTransformer.forward / BasicTransformerBlock._forward / CrossAttention.forward / FeedForward
  * (video_based/models/unet/attention.py:297-308, 247-251, 182-206, 44-65) in TWO launches that also store

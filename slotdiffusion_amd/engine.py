@@ -196,6 +196,40 @@ def slot_rollout(K, past_slots, pred_len, num_layers, num_heads, name='rollouter
 
 
 # ------------------------------------------------------------------------------------------
+# Physion VQA readout (vp_vqa/models/readout.py:56-87), composed from the GEMM kernel and framework ops: serves the
+# geometries sdmi_readout_fwd / _bwd refuse, and is the baseline they are checked and timed against
+# ------------------------------------------------------------------------------------------
+def readout_composed(slots, w1, b1, w2, b2, agg, op_dtype=torch.float32, label=None, loss_weight=1.0):
+    """slots [B, T, N, C]; w1 [F, 2C], b1 [F], w2 [1, F], b2 [1] (parameters: differentiated by autograd) ->
+    dict(logits [B], frame_logits [B, T], loss | None).  U | V = S [W_a; W_b]^T is ONE sdmi_igemm call with operands in
+    op_dtype and an fp32 result; the aggregate (max: over the gathered pair sums; sum / mean: the fixed slot weights),
+    linear2, the time max and the loss are torch ops."""
+    from . import kern
+    B, T, N, C = slots.shape
+    F = w1.shape[0]
+    wuv = w1.reshape(F, 2, C).permute(1, 0, 2).reshape(2 * F, C).to(op_dtype)
+    x = slots.reshape(B * T * N, C).to(op_dtype).contiguous()
+    uv = kern.MatmulNtFn.apply(x, wuv).reshape(B, T, N, 2, F)
+    if agg == 'max':
+        i, j = torch.triu_indices(N, N, 1, device=slots.device)         # itertools.combinations order
+        rel = (uv[:, :, i, 0] + uv[:, :, j, 1]).max(2)[0] + b1          # over [B, T, P, F]
+    else:                                # slot i is the first of N - 1 - i pairs and the second of i pairs
+        P = N * (N - 1) // 2
+        wu = torch.arange(N - 1, -1, -1, device=slots.device, dtype=uv.dtype).view(N, 1)
+        wv = torch.arange(N, device=slots.device, dtype=uv.dtype).view(N, 1)
+        rel = (uv[:, :, :, 0] * wu).sum(2) + (uv[:, :, :, 1] * wv).sum(2) + P * b1
+        rel = rel / P if agg == 'mean' else rel
+    # linear2 in fp64, rounded once: its F products cancel (sum aggregate: |logit| ~ 20 out of terms that add up to ~ 350
+    # in magnitude), and an fp32 dot product alone moves the logit by 1e-5; the kernel carries this sum in fp64 too
+    frame_logits = torch.nn.functional.linear(rel.double(), w2.double(), b2.double()).squeeze(-1).float()
+    logits = frame_logits.max(1)[0]
+    loss = None
+    if label is not None:
+        loss = loss_weight * torch.nn.functional.binary_cross_entropy_with_logits(logits, label.reshape(-1).type_as(logits))
+    return dict(logits=logits, frame_logits=frame_logits, loss=loss)
+
+
+# ------------------------------------------------------------------------------------------
 # a9-a11: LDM UNet (unet.py:551-576, 271-285; attention.py:297-308, 247-251, 182-206)
 # ------------------------------------------------------------------------------------------
 class UNetRunner:

@@ -192,6 +192,33 @@ def rollout_index_b(C, F):
     return _st_unit_index(ent)
 
 
+# Physion readout on sdmi_readout_fwd / sdmi_readout_bwd wherever the kernels cover the geometry (readout_covers); the
+# rest, and everything with this off (tests, tools/bench_readout.py), runs engine.readout_composed.  Not a policy
+# switch: the choice is geometric.
+_READOUT_FUSED = True
+READOUT_AGG = {'sum': _lib.ENUMS['SDMI_AGG_SUM'], 'mean': _lib.ENUMS['SDMI_AGG_MEAN'], 'max': _lib.ENUMS['SDMI_AGG_MAX']}
+_READOUT_INDEX = {}
+
+
+def readout_covers(N, C, F):
+    """Geometry of sdmi_readout_fwd / sdmi_readout_bwd (sdmi.h)."""
+    return 2 <= N <= 16 and 32 <= C <= 256 and C % 32 == 0 and 32 <= F <= 256 and F % 32 == 0
+
+
+def readout_pack_index(C, F, dtype, device='cpu'):
+    """int64 [F * 2C]: position in linear1.weight [F, 2C] (flat) of every element of the packed operand `w1p` of
+    sdmi_readout_fwd (sdmi.h) -- per 32-feature chunk and k step, the MFMA B fragments of W_a then W_b, lane by lane."""
+    key = (C, F, dtype, str(device))
+    if key not in _READOUT_INDEX:
+        kw, ke = (16, 8) if dtype == torch.bfloat16 else (8, 4)      # k per step, k per lane
+        ar = lambda n: torch.arange(n, device=device)
+        fc, ks, h, l, e = torch.meshgrid(ar(F // 32), ar(C // kw), ar(2), ar(64), ar(ke), indexing='ij')
+        row = 32 * fc + l % 32
+        col = h * C + kw * ks + ke * (l // 32) + e
+        _READOUT_INDEX[key] = (row * (2 * C) + col).reshape(-1)
+    return _READOUT_INDEX[key]
+
+
 def st_train_units(C):
     """Unit order of the training kernels' weight streams (csrc/st_train.hip), per wave: lists of
     (matrix key, first row, first k, transposed).  Forward: a = [proj_in | q | k | v], b = [to_out | q2 | to_out2 | per
@@ -831,6 +858,18 @@ class WeightBank:
                 src_b = torch.cat([wo.to(dtype).reshape(-1), w1_p.reshape(-1), w2.to(dtype).reshape(-1)])
                 vb = torch.cat([bo, w1_p.float().sum(1), w1 @ b2 + bb1, bb2]).contiguous()
                 self.cache[key] = dict(wa=wa, va=va, wb=src_b[ib].contiguous(), vb=vb, C=C, F=F)
+        return self.cache[key]
+
+    def readout_weights(self, dtype, name='linear1.weight'):
+        """linear1.weight [F, 2C] of the Physion readout as the packed operand of sdmi_readout_fwd / _bwd (sdmi.h) in
+        `dtype`: one gather out of the master (fp32) / shadow (bf16) arena.  Cached until the weights change."""
+        key = ('readout', name, dtype)
+        if key not in self.cache:
+            with torch.no_grad():
+                F, C2 = self.t[name].shape
+                src = self._flat(name, dtype)
+                idx = readout_pack_index(C2 // 2, F, dtype, src.device)
+                self.cache[key] = src.reshape(-1)[idx].contiguous()
         return self.cache[key]
 
     # ---- weight streams of the fused SpatialTransformer TRAINING kernels (sdmi.h: sdmi_st_train_fwd, sdmi_st_pack)
@@ -2461,6 +2500,94 @@ class TailTokensFn(torch.autograd.Function):
         dx = ops.zeros((B, Lp, D), dy.dtype, dy.device)
         _copy_rows(dy, 0, n * D, dx, (L - n) * D, Lp * D, B, n * D)
         return dx, None, None
+
+
+READOUT_NAMES = ('linear1.weight', 'linear1.bias', 'linear2.weight', 'linear2.bias')
+
+
+def readout_fwd(wb, slots, agg, label=None, loss_weight=1.0, names=READOUT_NAMES):
+    """sdmi_readout_fwd on the bank's weights: slots [B, T, N, C] fp32 / bf16 -> dict(frame_logits [B, T], logits [B],
+    t_star [B] int32, loss [1] | None, dlogit [B] | None).  Operands in the bank's dtype."""
+    w1p = wb.readout_weights(wb.dtype, names[0])
+    f = lambda n: wb.t[n].detach()
+    return ops.readout_fwd(slots, w1p, f(names[1]), f(names[2]).reshape(-1), f(names[3]), agg, wb.dtype, label=label,
+                           loss_weight=loss_weight)
+
+
+class ReadoutFn(torch.autograd.Function):
+    """PhysionReadout.forward (+ the BCE loss when `label` is given) as sdmi_readout_fwd, its backward as ONE
+    sdmi_readout_bwd that adds the four parameter gradients into the gradient arena.  -> (logits [B], frame_logits
+    [B, T], loss scalar | None).  Gradient may arrive through the loss (the fused dlogit, scaled on the device by
+    d loss) and / or through logits.  Slots are data (readout.py:56-79): no gradient reaches them."""
+
+    @staticmethod
+    def forward(ctx, slots, label, anchor, wb, agg, loss_weight=1.0, names=READOUT_NAMES):
+        assert not slots.requires_grad, 'PhysionReadout takes slots as data: no gradient flows to them'
+        r = readout_fwd(wb, slots, agg, label, loss_weight, names)
+        ctx.save_for_backward(slots, r['t_star'], r['dlogit'])
+        ctx.cfg = (wb, agg, names)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(r['frame_logits'])
+        return r['logits'], r['frame_logits'], (None if r['loss'] is None else r['loss'].reshape(()))
+
+    @staticmethod
+    def backward(ctx, dlogits, _dframes, dloss):
+        slots, t_star, dlogit = ctx.saved_tensors
+        wb, agg, names = ctx.cfg
+        gscale = None
+        if dloss is not None and dlogits is None:
+            d, gscale = dlogit, dloss.reshape(1).float().contiguous()
+        elif dloss is not None:
+            d = (dlogit * dloss.float() + dlogits.float()).contiguous()
+        elif dlogits is not None:
+            d = dlogits.float().contiguous()
+        else:
+            return (None,) * 7
+        dst = [_grads_of(wb, n) for n in names]
+        w1p = wb.readout_weights(wb.dtype, names[0])
+        ops.readout_bwd(slots, w1p, wb.t[names[1]].detach(), wb.t[names[2]].detach().reshape(-1), t_star, d, agg,
+                        wb.dtype, gscale=gscale, out=dst, accumulate=True)
+        return (None,) * 7
+
+
+class BceLogitsFn(torch.autograd.Function):
+    """loss_weight * binary_cross_entropy_with_logits(logits [B], label [B]) through the finisher launch of
+    sdmi_readout_fwd alone (phase 2 on the logits as a one-frame table): for logits that did not come with a loss."""
+
+    @staticmethod
+    def forward(ctx, logits, label, loss_weight=1.0):
+        r = ops.readout_finish(logits.detach().float().reshape(-1, 1).contiguous(), label, loss_weight)
+        ctx.save_for_backward(r['dlogit'])
+        return r['loss'].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogit,) = ctx.saved_tensors
+        out = torch.empty_like(dlogit)
+        call('sdmi_scale_dev', _st(), x=_p(dlogit), y=_p(out), s=_p(g.reshape(1).float().contiguous()),
+             dtype=_DT[dlogit.dtype], n=dlogit.numel())
+        return out, None, None
+
+
+class MatmulNtFn(torch.autograd.Function):
+    """y = x @ w^T in fp32 out of the implicit-GEMM kernel for an explicit weight TENSOR (engine.readout_composed);
+    gradient to w only (dw = dy^T x, the same kernel on transposed operands)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x)
+        return ops.linear(x, w.contiguous(), out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        M = x.shape[0]
+        Mp = (M + 7) // 8 * 8                          # the reduction length must be whole 16-byte vectors
+        dyt = torch.zeros((dy.shape[1], Mp), dtype=x.dtype, device=x.device)
+        dyt[:, :M] = dy.t()
+        xt = torch.zeros((x.shape[1], Mp), dtype=x.dtype, device=x.device)
+        xt[:, :M] = x.t()
+        return None, ops.linear(dyt, xt, out_dtype=torch.float32)
 
 
 class VaeAttnFn(torch.autograd.Function):

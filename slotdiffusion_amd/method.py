@@ -62,6 +62,41 @@ class SyntheticSlotsDataModule:
             yield {'slots': torch.randn(shape, generator=g).to(self.device)}
 
 
+class SyntheticSlotsLabelDataModule:
+    """`build_dataset` stand-in of the VQA readout (vp_vqa/datasets/physion.py: physion_slots_label_readout): seeded
+    random slots [B, video_len, N, D] with a 0 / 1 label that follows a planted rule the readout can represent --
+    label = 1 iff max_t max_{i<j} (<s_i, a> + <s_j, c>) > thr, with seeded directions a, c and thr the median of that
+    score under the slot distribution -- so a fit can be seen to learn."""
+
+    def __init__(self, params, steps_per_epoch=8, device='cuda', seed=1234):
+        self.params, self.steps_per_epoch, self.device, self.seed = params, steps_per_epoch, device, seed
+        self.rank = int(os.environ.get('RANK', 0))
+        rd = params.readout_dict
+        self.N, self.D, self.T = rd['num_slots'], rd['slot_size'], params.video_len
+        g = torch.Generator().manual_seed(seed)
+        self.a = torch.randn(self.D, generator=g) / self.D ** 0.5
+        self.c = torch.randn(self.D, generator=g) / self.D ** 0.5
+        self.thr = float(self.score(torch.randn((512, self.T, self.N, self.D), generator=g)).median())
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def score(self, slots):
+        """[B, T, N, D] -> [B]: max over frames and ordered pairs i < j of <s_i, a> + <s_j, c>."""
+        u, v = slots @ self.a, slots @ self.c                       # [B, T, N]
+        pair = u.unsqueeze(3) + v.unsqueeze(2)                      # [B, T, i, j]
+        keep = torch.ones(self.N, self.N).triu(1).bool()
+        return pair.masked_fill(~keep, float('-inf')).flatten(1).max(1)[0]
+
+    def train_loader(self, epoch=0):
+        shape = (self.params.train_batch_size, self.T, self.N, self.D)
+        g = torch.Generator().manual_seed(self.seed + 1000 * epoch + self.rank)
+        for _ in range(self.steps_per_epoch):
+            slots = torch.randn(shape, generator=g)
+            label = (self.score(slots) > self.thr).float()
+            yield {'slots': slots.to(self.device), 'label': label.to(self.device)}
+
+
 class Method:
     """fit() = epochs x steps of {forward, weighted loss, backward, (all-reduce), clip+Adam, hook}."""
 
@@ -84,7 +119,8 @@ class Method:
     # img_based/method.py:235-285 (SA / SADiffusion), video_based/method.py:291-341
     def _configure_optimizers(self):
         p = self.params
-        assert p.optimizer.lower() in ('adam', 'adamw') and p.weight_decay == 0., \
+        # (the readout config sets no weight_decay: nerv's BaseMethod defaults it to 0)
+        assert p.optimizer.lower() in ('adam', 'adamw') and self._get('weight_decay', 0.) == 0., \
             'the path covers Adam without weight decay (every shipped config)'
         total = p.max_epochs * len(self.datamodule)
         clip = self._get('clip_grad', 0) or 0

@@ -6,6 +6,7 @@ evaluation scripts can switch packages:
   LDM (model.dm_decoder) . slotdiffusion/img_based/models/ddpm/ldm.py:18-129, cond_ddpm.py:134-212
   VQVAEWrapper (.vae) .... slotdiffusion/video_based/models/vqvae/VQVAE.py:152-194
   LDMSlotFormer .......... slotdiffusion/vp_vqa/models/ldm_slotformer.py:14-215, slotformer.py:46-126
+  PhysionReadout ......... slotdiffusion/vp_vqa/models/readout.py:11-109
 Tensors cross this boundary in the reference's layout (NCHW fp32 images / latents, [B,N,D] slots);
 inside, everything is NHWC in the compute dtype (fp32 for parity runs, bf16 for throughput).
 """
@@ -1223,6 +1224,96 @@ class LDMSlotFormer(SADiffusion):
         pass
 
 
+class PhysionReadout(SlotModelBase):
+    """Linear relation readout of the Physion VQA task (registry name 'PhysionReadout', vp_vqa/models/readout.py:11-109):
+    linear1 on every slot pair of a frame, a symmetric aggregate over the pairs (sum / mean / max), linear2 to a
+    per-frame contact logit, the max over time; trained with BCE-with-logits on the video's label.  On the GPU this is
+    sdmi_readout_fwd (two launches, the loss fused in) and sdmi_readout_bwd (one) wherever they cover the geometry
+    (kern.readout_covers), engine.readout_composed otherwise.  Slots are data: no gradient flows to them."""
+    loss_names = ['vqa_loss']
+
+    def __init__(self, readout_dict=None, compute_dtype=None, seed=0):
+        r = dict(readout_dict or dict(num_slots=8, slot_size=192, agg_func='max', feats_dim=192))
+        assert r['agg_func'] in ('sum', 'mean', 'max')
+        assert r['num_slots'] >= 2, 'a pair readout needs two slots'
+        FlatModule.__init__(self, spec.physion_readout(r), seed=seed, lr_group_of=lambda name: 0)
+        self.readout_dict = r
+        self.num_slots, self.slot_size, self.agg_func = r['num_slots'], r['slot_size'], r['agg_func']
+        self.feats_dim = r['feats_dim']
+        # all slot pairs, flattened (readout.py:47-50): kept for checkpoint compatibility, the kernels enumerate the
+        # pairs themselves.  int64, so outside the fp32 arena; FlatModule._apply moves it with the model
+        n = self.num_slots
+        combs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+        self.register_buffer('comb_idx', torch.tensor(combs).long().flatten())
+        self.compute_dtype = compute_dtype or default_compute_dtype()
+        self._graph_cache = {}
+        self.step_seed = self.eval_seed = None
+
+    @property
+    def device(self):
+        return self.linear1.weight.device
+
+    @property
+    def dtype(self):
+        return self.linear1.weight.dtype
+
+    def _fused_ok(self, slots):
+        _, _, N, C = slots.shape
+        return kern._READOUT_FUSED and kern.readout_covers(N, C, self.feats_dim)
+
+    def forward(self, data_dict):
+        """readout.py:56-79: {'slots': [B, T, N, C]} -> {'logits': [B], 'frame_logits': [B, T]}.  With a 'label' in the
+        batch the loss is computed in the same launches and handed to calc_train_loss."""
+        slots = data_dict['slots']
+        assert slots.dim() == 4 and slots.shape[3] == self.slot_size, f'slots must be [B, T, N, {self.slot_size}]'
+        assert not slots.requires_grad, 'PhysionReadout takes slots as data: no gradient flows to them'
+        if slots.dtype not in (torch.float32, torch.bfloat16):
+            slots = slots.float()
+        slots = slots.contiguous()
+        label = data_dict.get('label')
+        if label is not None:
+            label = label.flatten().float()
+        grad = self.training and torch.is_grad_enabled()
+        bank = self.bank()
+        if self._fused_ok(slots):
+            if grad:
+                logits, frames, loss = kern.ReadoutFn.apply(slots, label, bank.anchor, bank, self.agg_func)
+            else:
+                r = kern.readout_fwd(bank, slots, self.agg_func, label)
+                logits, frames, loss = r['logits'], r['frame_logits'], r['loss']
+                loss = None if loss is None else loss.reshape(())
+        else:
+            with (contextlib.nullcontext() if grad else torch.no_grad()):
+                r = engine.readout_composed(slots, self.linear1.weight, self.linear1.bias, self.linear2.weight,
+                                            self.linear2.bias, self.agg_func, self.compute_dtype, label)
+            logits, frames, loss = r['logits'], r['frame_logits'], r['loss']
+        out = {'logits': logits, 'frame_logits': frames}
+        if loss is not None:
+            out['vqa_loss'] = loss
+        return out
+
+    def calc_train_loss(self, data_dict, out_dict):
+        """readout.py:81-87: {'vqa_loss': BCE-with-logits(logits, label)} -- the value the forward launches produced
+        when they saw the label, the finisher launch on the logits otherwise."""
+        if 'vqa_loss' in out_dict:
+            return {'vqa_loss': out_dict['vqa_loss']}
+        pred = out_dict['logits'].flatten()
+        gt = data_dict['label'].flatten().type_as(pred)
+        return {'vqa_loss': kern.BceLogitsFn.apply(pred, gt)}
+
+    @torch.no_grad()
+    def calc_eval_loss(self, data_dict, out_dict):
+        """readout.py:89-101: the loss plus the accuracy at thresholds 0.1, 0.3 .. 0.9 on sigmoid(logit)."""
+        import numpy as np
+        ret_dict = {k: v.detach() for k, v in self.calc_train_loss(data_dict, out_dict).items()}
+        pred = out_dict['logits'].flatten()
+        gt = data_dict['label'].flatten().type_as(pred)
+        pred_probs = torch.sigmoid(pred)
+        for thresh in np.arange(0.1, 1, 0.2):
+            ret_dict[f'acc_{thresh:.2f}'] = (pred_probs > thresh).eq(gt).float().mean()
+        return ret_dict
+
+
 def build_model(params):
     """Registry (img_based/models/__init__.py:12-39, video_based/models/__init__.py:12-33) for the
     hot-path models."""
@@ -1248,4 +1339,10 @@ def build_model(params):
         return LDMSlotFormer(resolution=params.resolution, clip_len=params.input_frames,
                              slot_dict=params.slot_dict, dec_dict=params.dec_dict,
                              rollout_dict=params.rollout_dict, loss_dict=params.loss_dict)
+    if params.model == 'PhysionReadout':       # vp_vqa/models/__init__.py:19-20
+        rd = params.get('readout_dict') if hasattr(params, 'get') else getattr(params, 'readout_dict', None)
+        if rd is None:
+            raise NotImplementedError('PhysionReadout is not on the MI355X hot path yet for params without a '
+                                      'readout_dict (num_slots, slot_size, agg_func, feats_dim)')
+        return PhysionReadout(readout_dict=rd)
     raise NotImplementedError(f'{params.model} is not on the MI355X hot path yet')

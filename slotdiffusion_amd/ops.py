@@ -704,3 +704,73 @@ def mse(pred, target, want_grad=False, gscale=1.0, l1=False, oscale=0.0):
          partial=_p(partial), dtype=_dt(pred), n=n, nblk=nblk, gscale=gscale, l1=int(l1),
          oscale=float(oscale))
     return (out, dpred) if want_grad else out
+
+
+# ------------------------------------------------------------------------------------------
+# Physion VQA readout (sdmi.h: sdmi_readout_fwd / sdmi_readout_bwd)
+# ------------------------------------------------------------------------------------------
+def _agg(agg):
+    return {'sum': 0, 'mean': 1, 'max': 2}[agg] if isinstance(agg, str) else int(agg)
+
+
+def readout_fwd(slots, w1p, b1, w2, b2, agg, op_dtype, label=None, loss_weight=1.0, phase=0, frame_logits=None):
+    """slots [B, T, N, C] (fp32 / bf16, contiguous), w1p: linear1.weight packed in op_dtype (kern.readout_pack_index)
+    -> dict(frame_logits, logits, t_star, loss, dlogit); loss / dlogit are None without a label."""
+    _need_gpu(slots, w1p)
+    slots = slots.contiguous()
+    B, T, N, C = slots.shape
+    dev = slots.device
+    if frame_logits is None:
+        frame_logits = torch.empty((B, T), dtype=torch.float32, device=dev)
+    logits = torch.empty((B,), dtype=torch.float32, device=dev)
+    t_star = torch.empty((B,), dtype=torch.int32, device=dev)
+    loss = dlogit = None
+    if label is not None:
+        label = label.reshape(-1).float().contiguous()
+        assert label.numel() == B
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dlogit = torch.empty((B,), dtype=torch.float32, device=dev)
+    call('sdmi_readout_fwd', _stream(), slots=_p(slots), w1p=_p(w1p), b1=_p(b1), w2=_p(w2), b2=_p(b2), label=_p(label),
+         frame_logits=_p(frame_logits), logits=_p(logits), t_star=_p(t_star), loss=_p(loss), dlogit=_p(dlogit),
+         B=B, T=T, N=N, C=C, F=b1.numel(), agg=_agg(agg), x_dtype=_dt(slots), op_dtype=_DT[op_dtype], phase=phase,
+         loss_weight=float(loss_weight),
+         _meta=dict(flops=4.0 * B * T * N * C * b1.numel(),
+                    bytes=float(slots.numel() * slots.element_size() + w1p.numel() * w1p.element_size() + 4 * B * T)))
+    return dict(frame_logits=frame_logits, logits=logits, t_star=t_star, loss=loss, dlogit=dlogit)
+
+
+def readout_finish(frame_logits, label=None, loss_weight=1.0):
+    """The finisher launch alone: frame_logits [B, T] fp32 -> max over time, t_star, BCE-with-logits and dlogit."""
+    _need_gpu(frame_logits)
+    B, T = frame_logits.shape
+    dev = frame_logits.device
+    logits = torch.empty((B,), dtype=torch.float32, device=dev)
+    t_star = torch.empty((B,), dtype=torch.int32, device=dev)
+    loss = dlogit = None
+    if label is not None:
+        label = label.reshape(-1).float().contiguous()
+        assert label.numel() == B
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dlogit = torch.empty((B,), dtype=torch.float32, device=dev)
+    # (phase 2 reads no slot or weight: the geometry fields only have to pass the argument check)
+    fl = _p(frame_logits)
+    call('sdmi_readout_fwd', _stream(), slots=fl, w1p=fl, b1=fl, w2=fl, b2=fl, label=_p(label), frame_logits=fl,
+         logits=_p(logits), t_star=_p(t_star), loss=_p(loss), dlogit=_p(dlogit), B=B, T=T, N=2, C=32, F=32, agg=2,
+         x_dtype=_DT[torch.float32], op_dtype=_DT[torch.float32], phase=2, loss_weight=float(loss_weight))
+    return dict(frame_logits=frame_logits, logits=logits, t_star=t_star, loss=loss, dlogit=dlogit)
+
+
+def readout_bwd(slots, w1p, b1, w2, t_star, dlogit, agg, op_dtype, gscale=None, out=None, accumulate=False):
+    """-> (dW1 [F, 2C], db1 [F], dW2 [F], db2 [1]) fp32; `out`: four destinations (accumulate=True adds to them)."""
+    _need_gpu(slots, w1p, dlogit)
+    slots = slots.contiguous()
+    B, T, N, C = slots.shape
+    F = b1.numel()
+    if out is None:
+        assert not accumulate
+        out = [torch.empty(s, dtype=torch.float32, device=slots.device) for s in ((F, 2 * C), (F,), (F,), (1,))]
+    call('sdmi_readout_bwd', _stream(), slots=_p(slots), w1p=_p(w1p), b1=_p(b1), w2=_p(w2), t_star=_p(t_star),
+         dlogit=_p(dlogit), gscale=_p(gscale), dw1=_p(out[0]), db1=_p(out[1]), dw2=_p(out[2]), db2=_p(out[3]),
+         B=B, T=T, N=N, C=C, F=F, agg=_agg(agg), x_dtype=_dt(slots), op_dtype=_DT[op_dtype], accumulate=int(accumulate),
+         _meta=dict(flops=4.0 * B * N * C * F, bytes=float(B * N * C * slots.element_size() * (F // 4) + 8 * F * C)))
+    return tuple(out)

@@ -22,6 +22,7 @@ Reference layouts restated (names only, no code shared):
   DDPM schedule buffers ..... video_based/models/ddpm/ddpm.py:69-131
   TransformerPredictor ...... video_based/models/predictor.py:20-44
   SlotRollouter ............. vp_vqa/models/slotformer.py:46-81
+  PhysionReadout ............ vp_vqa/models/readout.py:39-54
 """
 from collections import namedtuple
 
@@ -495,3 +496,11 @@ def ldm_slotformer(slot_dict, dec_dict, rollout_dict):
     assert rollout_dict['slot_size'] == slot_dict['slot_size'] and rollout_dict['num_slots'] == slot_dict['num_slots']
     dec = [p._replace(trainable=False) for p in ldm('dm_decoder', dec_dict)]
     return dec + slot_rollouter('rollouter', rollout_dict)
+
+
+def physion_readout(readout_dict):
+    """PhysionReadout (vp_vqa/models/readout.py:39-54): linear1 over a slot pair, linear2 to the logit.  The int64
+    `comb_idx` buffer is not part of the fp32 arena: the model registers it itself (it is the root's own buffer, so it
+    comes first in the state dict either way)."""
+    r = readout_dict
+    return linear('linear1', 2 * r['slot_size'], r['feats_dim']) + linear('linear2', r['feats_dim'], 1)

@@ -1,7 +1,7 @@
 """Registry module with the surface of `slotdiffusion.vp_vqa` (scripts/train.py:97-100): video prediction with
-LDMSlotFormer.  The Physion readout / VQA models stay out of scope."""
+LDMSlotFormer, and the VQA readout on its rollouts with PhysionReadout."""
 from .. import models as _models
-from ..method import SyntheticSlotsDataModule, build_method  # noqa: F401
+from ..method import SyntheticSlotsDataModule, SyntheticSlotsLabelDataModule, build_method  # noqa: F401
 
 
 def build_model(params):
@@ -10,9 +10,12 @@ def build_model(params):
         return _models.LDMSlotFormer(resolution=params.resolution, clip_len=params.input_frames,
                                      slot_dict=params.slot_dict, dec_dict=params.dec_dict,
                                      rollout_dict=params.rollout_dict, loss_dict=params.loss_dict)
-    raise NotImplementedError(f'{params.model} is not on the MI355X hot path yet')
+    return _models.build_model(params)          # PhysionReadout (needs params.readout_dict); refusals by name
 
 
 def build_dataset(params, val_only=False):
-    """Datasets are out of scope; synthetic slots [B, history + rollout, N, D]."""
+    """Datasets are out of scope; synthetic slots [B, history + rollout, N, D], for the readout
+    [B, video_len, N, D] with a label."""
+    if params.model == 'PhysionReadout':
+        return SyntheticSlotsLabelDataModule(params)
     return SyntheticSlotsDataModule(params)

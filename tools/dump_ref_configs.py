@@ -14,9 +14,9 @@ REF = '/root/reference/slotdiffusion'
 OUT = os.path.join(HERE, '..', 'tests', 'golden', 'configs')
 PATTERNS = ['img_based/configs/sa/*.py', 'img_based/configs/sa_ldm/*.py',
             'video_based/configs/savi/*.py', 'video_based/configs/savi_ldm/*.py']
-# the third task's config goes to a directory of its own, under its own file name (tests/golden/configs/ is pinned to the
+# the third task's configs go to a directory of its own, under their own file names (tests/golden/configs/ is pinned to the
 # img_based / video_based set)
-VP_VQA = 'vp_vqa/configs/ldmslotformer_physion_params-res128.py'
+VP_VQA = ['vp_vqa/configs/ldmslotformer_physion_params-res128.py', 'vp_vqa/configs/readout_physion_params.py']
 
 
 def plain(v):
@@ -44,14 +44,15 @@ def main():
                 json.dump(d, f, indent=1, sort_keys=True)
             n += 1
             print(task, name, d.get('model'))
-    path = os.path.join(REF, VP_VQA)
-    d = plain(compat.load_params(path).to_dict())
-    d['_task'], d['_source'] = 'vp_vqa', os.path.relpath(path, '/root/reference')
-    os.makedirs(os.path.join(OUT, '..', 'vp_vqa'), exist_ok=True)
-    with open(os.path.join(OUT, '..', 'vp_vqa', os.path.basename(path)[:-3] + '.json'), 'w') as f:
-        json.dump(d, f, indent=1, sort_keys=True)
-    print('vp_vqa', os.path.basename(path)[:-3], d.get('model'))
-    print(n + 1, 'configs')
+    for cfg in VP_VQA:
+        path = os.path.join(REF, cfg)
+        d = plain(compat.load_params(path).to_dict())
+        d['_task'], d['_source'] = 'vp_vqa', os.path.relpath(path, '/root/reference')
+        os.makedirs(os.path.join(OUT, '..', 'vp_vqa'), exist_ok=True)
+        with open(os.path.join(OUT, '..', 'vp_vqa', os.path.basename(path)[:-3] + '.json'), 'w') as f:
+            json.dump(d, f, indent=1, sort_keys=True)
+        print('vp_vqa', os.path.basename(path)[:-3], d.get('model'))
+    print(n + len(VP_VQA), 'configs')
 
 
 if __name__ == '__main__':

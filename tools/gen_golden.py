@@ -969,7 +969,75 @@ def main_slotformer():
         print(k, v.shape, v.dtype)
 
 
+def main_readout():
+    """tests/golden/physion_readout_b3.npz + tests/golden/vp_vqa/readout_keys.json.gz: the Physion VQA readout of the
+    reference's third task (vp_vqa: PhysionReadout, readout_physion_params: 8 slots x 192, feats_dim 192).  Weights
+    det-filled by state-dict position (comb_idx keeps its values), seeded slots [3, 5, 8, 192] and labels [3]; for
+    every agg_func: logits, vqa_loss, the acc_* of calc_eval_loss and the four parameter gradients of the loss
+    (linear1.weight.grad as every 4th row).  Precondition of the fixture, searched over seeds and re-asserted by the CPU
+    test: evaluated in fp64 the top-two gap of the max over time is >= 1e-3 for every sample and, at every winning
+    frame, the top-two gap of the max over pairs is >= 1e-4 for every feature."""
+    import gzip
+    import json
+    from tests import readout_ref as R
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    vm = rh.ref_models('vp_vqa')
+    skip = lambda n: n == 'comb_idx'
+    B, T = 3, 5
+
+    def make(agg):
+        P = rh.ref_params('vp_vqa', '', 'readout_physion_params')
+        P.readout_dict['agg_func'] = agg
+        model = vm.build_model(P)
+        det_fill_(model.state_dict().items(), skip=skip)
+        return model, P
+
+    model, P = make('max')
+    keys = {'state': [[k, list(v.shape), str(v.dtype)] for k, v in model.state_dict().items()],
+            'buffers': [k for k, _ in model.named_buffers()],
+            'comb_idx': model.comb_idx.tolist(), 'num_params': sum(p.numel() for p in model.parameters())}
+    os.makedirs(os.path.join(OUT, 'vp_vqa'), exist_ok=True)
+    with open(os.path.join(OUT, 'vp_vqa', 'readout_keys.json.gz'), 'wb') as f:
+        with gzip.GzipFile(fileobj=f, mode='wb', mtime=0) as gz:        # (mtime=0: the file regenerates bit-identically)
+            gz.write(json.dumps(keys, sort_keys=True).encode())
+    W = {k: v.detach().clone() for k, v in model.state_dict().items() if k != 'comb_idx'}
+    N, D = P.readout_dict['num_slots'], P.readout_dict['slot_size']
+    for seed in range(100):
+        slots = torch.randn(B, T, N, D, generator=torch.Generator().manual_seed(seed))
+        g = [R.gaps(W, slots, agg) for agg in R.AGGS]
+        if all(t >= 1e-3 and p >= 1e-4 for t, p in g):
+            break
+    else:
+        raise SystemExit('no seed meets the gap condition')
+    label = torch.tensor([1., 0., 1.])
+    G = dict(slots=slots, label=label, seed=torch.tensor(seed),
+             gaps=torch.tensor([[t, min(p, 1e30)] for t, p in g], dtype=torch.float64))
+    for agg in R.AGGS:
+        model, _ = make(agg)
+        model.train()
+        data = dict(slots=slots, label=label)
+        out = model(data)
+        loss = model.calc_train_loss(data, out)['vqa_loss']
+        loss.backward()
+        G[f'{agg}:logits'] = out['logits'].detach()
+        for k, v in model.calc_eval_loss(data, {'logits': out['logits'].detach()}).items():
+            G[f'{agg}:{k}'] = v.detach()
+        named = dict(model.named_parameters())
+        G[f'{agg}:grad_rows4:linear1.weight'] = named['linear1.weight'].grad[::4].clone()
+        for n in ('linear1.bias', 'linear2.weight', 'linear2.bias'):
+            G[f'{agg}:grad:{n}'] = named[n].grad.clone()
+    arrs = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in G.items()}
+    np.savez_compressed(os.path.join(OUT, 'physion_readout_b3.npz'), **arrs)
+    print('seed', seed, 'gaps (time, pair) per agg', g)
+    for k, v in arrs.items():
+        print(k, v.shape, v.dtype)
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'readout':
+        main_readout()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'slotformer':
         main_slotformer()
         sys.exit(0)
