@@ -69,6 +69,22 @@ def _make_struct(name, fields):
 
 CSTRUCT = {n: _make_struct(n, f) for n, f in STRUCTS.items()}
 
+
+
+def struct_array(struct_name, rows):
+    """ctypes array of `struct_name`, one element per dict of `rows` (missing fields = 0): the HOST tables that some
+    entry points take by address (`ctypes.addressof`)."""
+    rows = list(rows)
+    names = {f for f, _ in STRUCTS[struct_name]}
+    arr = (CSTRUCT[struct_name] * len(rows))()
+    for a, r in zip(arr, rows):
+        for k, v in r.items():
+            if k not in names:
+                raise KeyError(f'{struct_name} has no field {k}')
+            setattr(a, k, v)
+    return arr
+
+
 _lib = None
 
 

@@ -12,11 +12,14 @@ operands views of the bf16 shadow arena (same offsets); only channel-padded and 
 fused operands are materialised.
 """
 import contextlib
+import ctypes
 import os
+from types import SimpleNamespace
 
+import numpy as np
 import torch
 
-from . import _lib, ops, policy
+from . import _lib, derived, ops, policy
 from ._lib import call
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
@@ -81,15 +84,16 @@ _ST_ROWS = 0
 
 def _copy_group(items):
     """[(src ptr, dst ptr, bytes)] -> sdmi_copy_group launches of up to 32 copies each."""
-    import ctypes
-    Item = _lib.CSTRUCT['SdmiCopyItem']
     for c0 in range(0, len(items), 32):
-        chunk = items[c0:c0 + 32]
-        arr = (Item * len(chunk))()
-        for a, (sp, dp, nb) in zip(arr, chunk):
-            a.src, a.dst, a.bytes = sp, dp, nb
-        call('sdmi_copy_group', _st(), items=ctypes.addressof(arr), n=len(chunk))
+        arr = _lib.struct_array('SdmiCopyItem', (dict(src=sp, dst=dp, bytes=nb) for sp, dp, nb in items[c0:c0 + 32]))
+        call('sdmi_copy_group', _st(), items=ctypes.addressof(arr), n=len(arr))
 
+
+def _scatter_add(segs):
+    """[(src ptr, dst ptr, fp32 count)]: dst += src, one sdmi_scatter_add launch per 32 segments."""
+    for c0 in range(0, len(segs), 32):
+        arr = _lib.struct_array('SdmiScatterItem', (dict(src=sp, dst=dp, count=cnt) for sp, dp, cnt in segs[c0:c0 + 32]))
+        call('sdmi_scatter_add', _st(), items=ctypes.addressof(arr), n=len(arr))
 
 
 # ------------------------------------------------------------------------------------------
@@ -100,7 +104,6 @@ def _st_unit_index(entries):
     """entries[w] = [(element offset of the matrix, row pitch, first row, first k), ...] per unit, 8 waves
     -> int64 [8 * U * 1024] gather index into the flat source (unit byte b of wave w, unit u at
     ((w * U + u) * 1024 + b / 2)): physical 16-byte chunk p of row r holds logical chunk p ^ ((r >> 1) & 7)."""
-    import numpy as np
     r = np.arange(16, dtype=np.int64)[:, None, None]
     p_ = np.arange(8, dtype=np.int64)[None, :, None]
     e = np.arange(8, dtype=np.int64)[None, None, :]
@@ -253,6 +256,19 @@ def st_train_units(C):
     return out
 
 
+def st_pack_descs(rows, units, mats, dst):
+    """Fill `rows` (records of SdmiStPackDesc) for one unit stream: `units` (st_train_units, per wave) of the bf16
+    matrices `mats` into the stream tensor `dst`, 2 KB per unit."""
+    base = dst.data_ptr()
+    for i, (key, r0, k0, tr) in enumerate(u for wave in units for u in wave):
+        m = mats[key]
+        ld = m.shape[1]
+        if tr:      # unit rows walk the matrix's columns: element (r, k) = M[k0 + k][r0 + r]
+            derived.put(rows, i, src=m.data_ptr() + 2 * (k0 * ld + r0), dst=base + i * 2048, rs=1, cs=ld)
+        else:
+            derived.put(rows, i, src=m.data_ptr() + 2 * (r0 * ld + k0), dst=base + i * 2048, rs=ld, cs=1)
+
+
 def ups_parity_split(w):
     """Nearest-2x upsampling followed by a 3x3 convolution (unet.py:108-121) reads only 2 x 2 DISTINCT input pixels
     per output pixel: output parity (py, px) is a 2 x 2 convolution of the low-resolution input whose taps are sums
@@ -314,14 +330,19 @@ class WeightBank:
         # gradient destinations a side-stream launch of this backward wrote: a main-stream writer of the same
         # destination (pair launch, pending fold) waits for that stream first
         self._side_dst = {}
-        # dgrad operands: key -> [buffer, epoch, (stable source view | None, geometry)]
-        self._wd, self._wd_epoch, self._wd_stale, self._wd_table = {}, 0, False, None
-        # e4m3fn operands with device-side scales (training in the fp8 configuration): name -> [bytes, inv view, epoch,
-        # source view]; one slot of _w8_amax / _w8_inv per operand, in registration order
-        self._w8, self._w8_epoch, self._w8_stale, self._w8_table = {}, 0, False, None
-        self._w8_amax = self._w8_inv = None
-        # unit streams of the fused SpatialTransformer training kernels: block -> dict(wa, wb, descs, epoch)
-        self._stp, self._stp_epoch, self._stp_stale, self._stp_table = {}, 0, False, None
+        self._cq, self._wq_flushes, self._fz = [], 0, None
+        # derived operands re-made once per optimiser step, each family by ONE launch over its device-side descriptor
+        # table (derived.StepTable): dgrad operands (wd / wd_sub, one table per dtype), e4m3fn operands with device-side
+        # scales (w8_dev: descriptor i = slot i of _q_amax / _q_inv) and the unit streams of the fused
+        # SpatialTransformer training kernels (st_train_streams)
+        self.dgrad_ops = derived.StepTable('dgrad operand', 'SdmiPackDesc', self._dgrad_fill, self._dgrad_launch,
+                                           self._dgrad_first, self._arena_ptrs)
+        self._q_amax = self._q_inv = None
+        self.fp8_ops = derived.StepTable('fp8 operand', 'SdmiFp8Desc', self._fp8_fill, self._fp8_launch,
+                                         lambda m, one: self._fp8_launch(None, one(), m.slot),       # on its own slot
+                                         lambda: self._arena_ptrs() + (_p(self._q_amax), _p(self._q_inv)))
+        self.st_streams = derived.StepTable('fused training block', 'SdmiStPackDesc', self._st_fill, self._st_launch,
+                                            lambda m, one: self._st_launch(None, one()), self._arena_ptrs)
 
     def anchor_for(self, names):
         n = names if isinstance(names, str) else names[0]
@@ -375,26 +396,21 @@ class WeightBank:
         ws_len = sum(sp * (kw['N'] * kw['K'] + kw['N']) for (kw, _, _), sp in zip(q, splits) if sp > 1)
         dev = keep[0].device
         ws = torch.empty((max(ws_len, 1),), dtype=torch.float32, device=dev)
-        Arr = _lib.CSTRUCT['SdmiWgradArgs'] * len(q)
-        arr = Arr()
-        off = 0
-        flops = 0.0
-        for a, (kw, _, _), sp in zip(arr, q, splits):
-            for k, v in kw.items():
-                setattr(a, k, v)
-            a.splits = sp
+        off, rows = 0, []
+        for (kw, _, _), sp in zip(q, splits):
+            rows.append(dict(kw, splits=sp))
             if sp > 1:
-                a.workspace = ws.data_ptr() + 4 * off
+                rows[-1]['workspace'] = ws.data_ptr() + 4 * off
                 off += sp * (kw['N'] * kw['K'] + kw['N'])
-            flops += 2.0 * kw['M'] * kw['N'] * kw['K']
-        self._wq_flushes = getattr(self, '_wq_flushes', 0) + 1
+        arr = _lib.struct_array('SdmiWgradArgs', rows)
+        flops = sum(2.0 * kw['M'] * kw['N'] * kw['K'] for kw, _, _ in q)
+        self._wq_flushes += 1
         side = self.side_stream(f'wgrad-group-{self._wq_flushes % self.n_side}')
         if side is not None:
             ev = torch.cuda.Event()
             ev.record()
             side.wait_event(ev)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            import ctypes
             call('sdmi_wgrad_group', _st(), problems=ctypes.addressof(arr), n=len(q),
                  _meta=dict(flops=flops))
         self._pending.append(tuple(keep) + (ws,))
@@ -402,17 +418,11 @@ class WeightBank:
 
     # ---- deferred dgamma / dbeta folds of the normalisation backward passes ---------------------
     def queue_colsum(self, partial, nblk, C, out0, out1):
-        self._cq = getattr(self, '_cq', [])
         self._cq.append((partial, nblk, C, out0, out1))
         self.ensure_join()
 
     def flush_colsum(self):
-        q = getattr(self, '_cq', [])
-        if not q:
-            return
-        self._cq = []
-        import ctypes
-        Item = _lib.CSTRUCT['SdmiColsumItem']
+        q, self._cq = self._cq, []
         # a parameter used several times per step (Slot Attention iterations, per-frame modules)
         # has several items with the same destination: they go to successive launches (the
         # workgroups of one launch read-modify-write their destinations concurrently)
@@ -427,9 +437,8 @@ class WeightBank:
             ch[0].append(it)
             ch[1].add(_p(it[3]))
         for chunk, _ in chunks:
-            arr = (Item * len(chunk))()
-            for a, (partial, nblk, C, o0, o1) in zip(arr, chunk):
-                a.partial, a.out0, a.out1, a.nblk, a.C = _p(partial), _p(o0), _p(o1), nblk, C
+            arr = _lib.struct_array('SdmiColsumItem', (dict(partial=_p(partial), out0=_p(o0), out1=_p(o1), nblk=nblk, C=C)
+                                                       for partial, nblk, C, o0, o1 in chunk))
             call('sdmi_colsum_group', _st(), items=ctypes.addressof(arr), n=len(chunk))
         # (the partial buffers die with q: the launches above are ordered before their reuse)
 
@@ -444,10 +453,7 @@ class WeightBank:
             return
         self._pfold = None
         self._after_side_writers(pf[0]['dw'], pf[0]['dbias'])
-        import ctypes
-        arr = (_lib.CSTRUCT['SdmiWgradArgs'] * 1)()
-        for k, v in pf[0].items():
-            setattr(arr[0], k, v)
+        arr = _lib.struct_array('SdmiWgradArgs', [pf[0]])
         call('sdmi_wgrad_fold_group', _st(), problems=ctypes.addressof(arr), n=1)
 
     def _after_side_writers(self, *ptrs):
@@ -461,7 +467,6 @@ class WeightBank:
         """One sdmi_bwd_pair launch: dkw / wkw are the sdmi_igemm / sdmi_wgrad fields of the layer's data
         and weight gradient; M-split chosen here (the weight-gradient workgroups take what the data
         gradient leaves of `pair_slots` resident workgroups, >= pair_min_steps 64-row steps each)."""
-        import ctypes
         M, N, K = wkw['M'], wkw['N'], wkw['K']
         t128 = ((dkw['M'] + 127) // 128) * ((dkw['N'] + 127) // 128)
         shallow = dkw['KH'] == 1 and dkw['KW'] == 1 and dkw['K'] * 2 <= 512
@@ -485,18 +490,12 @@ class WeightBank:
         ws = None
         if splits > 1:
             ws = torch.empty((splits * (N * K + N),), dtype=torch.float32, device=keep[0].device)
-        S = _lib.CSTRUCT
-        d, w, f = S['SdmiGemmArgs'](), S['SdmiWgradArgs'](), S['SdmiWgradArgs']()
-        for k, v in dkw.items():
-            setattr(d, k, v)
-        for k, v in wkw.items():
-            setattr(w, k, v)
-        w.splits, w.workspace, w.defer_fold = splits, _p(ws), 1
         pf, self._pfold = self._pfold, None
         if pf is not None:
             self._after_side_writers(pf[0]['dw'], pf[0]['dbias'])
-            for k, v in pf[0].items():
-                setattr(f, k, v)
+        d = _lib.struct_array('SdmiGemmArgs', [dkw])
+        w = _lib.struct_array('SdmiWgradArgs', [dict(wkw, splits=splits, workspace=_p(ws), defer_fold=1)])
+        f = _lib.struct_array('SdmiWgradArgs', [pf[0]]) if pf is not None else None
         call('sdmi_bwd_pair', _st(), dgrad=ctypes.addressof(d), wgrad=ctypes.addressof(w),
              fold=(ctypes.addressof(f) if pf is not None else 0), dgrad_cap=((n_d + 7) // 8 * 8), wgrad_tile=wt,
              _meta=dict(flops=2.0 * dkw['M'] * dkw['N'] * dkw['K'] + 2.0 * M * N * K,
@@ -530,15 +529,18 @@ class WeightBank:
             if names is not None and all(n in fz for n in names):
                 keep[key] = val
         self.cache = keep
-        self._wd_stale = True
-        self._w8_stale = True
-        self._stp_stale = True
+        for fam in (self.dgrad_ops, self.fp8_ops, self.st_streams):
+            fam.mark_stale()
 
     def _frozen_names(self):
-        fz = getattr(self, '_fz', None)
-        if fz is None:
-            fz = self._fz = {p.name for p in getattr(self.model, '_spec', []) if not p.trainable}
-        return fz
+        if self._fz is None:
+            self._fz = {p.name for p in getattr(self.model, '_spec', []) if not p.trainable}
+        return self._fz
+
+    def _arena_ptrs(self):
+        """Base pointers of the arenas the derived operands are made from (derived.StepTable's source check)."""
+        m = self.model
+        return (m.arena().data_ptr(), m.shadow_arena().data_ptr() if m.compute_dtype != torch.float32 else None)
 
     def f(self, name):
         return self.t[name]
@@ -644,66 +646,29 @@ class WeightBank:
         them from the fp32 master arena with one sdmi_fp8_quant_group call (memset + amax launch + quantise launch,
         descriptor table on the device, no read-back) -- part of the captured train step, so every replay
         quantises the weights it multiplies with."""
-        if self._w8_stale:
-            self._requant_all()
-        ent = self._w8.get(name)
-        if ent is not None and ent[2] == self._w8_epoch:
-            return ent[0], ent[1]
-        flat = self._flat(name, torch.float32)
-        if flat is None or flat.numel() % 16:
-            raise _lib.SdmiError(f'{name}: fp8 operands need 16-byte input-channel rows')
-        if self._w8_amax is None:
-            self._w8_amax = torch.zeros(self.W8_SLOTS, dtype=torch.int32, device=flat.device)
-            self._w8_inv = torch.zeros(self.W8_SLOTS, dtype=torch.float32, device=flat.device)
-        if ent is None:
-            idx = len(self._w8)
-            if idx >= self.W8_SLOTS:
+        m = self.fp8_ops.get(name)
+        if m is None:
+            flat = self._flat(name, torch.float32)
+            if flat is None or flat.numel() % 16:
+                raise _lib.SdmiError(f'{name}: fp8 operands need 16-byte input-channel rows')
+            if self._q_amax is None:
+                self._q_amax = torch.zeros(self.W8_SLOTS, dtype=torch.int32, device=flat.device)
+                self._q_inv = torch.zeros(self.W8_SLOTS, dtype=torch.float32, device=flat.device)
+            slot = len(self.fp8_ops.members)
+            if slot >= self.W8_SLOTS:
                 raise _lib.SdmiError('fp8 operand table full')
-            ent = [torch.empty(flat.shape, dtype=torch.uint8, device=flat.device), self._w8_inv[idx:idx + 1],
-                   self._w8_epoch, flat, idx]
-            self._w8[name] = ent
-            self._w8_table = None             # new member: rebuild the descriptor table at the next re-quantisation
-        # (first use: a one-entry table -- eager only, it copies the table to the device)
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.SdmiError(f'{name}: first fp8 use of a weight inside a graph capture (its descriptor table is '
-                                 'a host-to-device copy): run the warm-up passes before capturing')
-        Desc = _lib.CSTRUCT['SdmiFp8Desc']
-        arr = (Desc * 1)()
-        blocks = self._fill_desc8(arr[0], ent, 0)
-        dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(flat.device)
-        idx = ent[4]
-        call('sdmi_fp8_quant_group', _st(), descs=_p(dev), n_desc=1, src_dtype=_lib.F32, total_blocks=blocks,
-             amax_bits=_p(self._w8_amax[idx:]), inv_scale=_p(self._w8_inv[idx:]))
-        ent[2] = self._w8_epoch
-        return ent[0], ent[1]
+            m = self.fp8_ops.add(name, SimpleNamespace(q=torch.empty(flat.shape, dtype=torch.uint8, device=flat.device),
+                                                       inv=self._q_inv[slot:slot + 1], src=flat, slot=slot), flat.device)
+        return m.q, m.inv
 
     @staticmethod
-    def _fill_desc8(d, e, blk):
-        d.src, d.dst, d.n, d.block_begin = e[3].data_ptr(), e[0].data_ptr(), e[3].numel(), blk
-        return blk + (e[3].numel() + 4095) // 4096
+    def _fp8_fill(m, rows, blk):
+        derived.put(rows, 0, src=m.src.data_ptr(), dst=m.q.data_ptr(), n=m.src.numel(), block_begin=blk)
+        return blk + (m.src.numel() + 4095) // 4096
 
-    def _requant_all(self):
-        self._w8_stale = False
-        if not self._w8:
-            return
-        self._w8_epoch += 1
-        items = sorted(self._w8.values(), key=lambda e: e[4])         # slot order = descriptor order
-        if self._w8_table is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.SdmiError('fp8 descriptor table rebuilt inside a graph capture (a new fp8 operand was '
-                                     'registered after the warm-up passes)')
-            Desc = _lib.CSTRUCT['SdmiFp8Desc']
-            arr = (Desc * len(items))()
-            blk = 0
-            for d, e in zip(arr, items):
-                blk = self._fill_desc8(d, e, blk)
-            dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(items[0][0].device)
-            self._w8_table = (dev, len(items), blk)
-        tab = self._w8_table
-        call('sdmi_fp8_quant_group', _st(), descs=_p(tab[0]), n_desc=tab[1], src_dtype=_lib.F32, total_blocks=tab[2],
-             amax_bits=_p(self._w8_amax), inv_scale=_p(self._w8_inv))
-        for e in items:
-            e[2] = self._w8_epoch
+    def _fp8_launch(self, _, tab, slot=0):
+        call('sdmi_fp8_quant_group', _st(), descs=_p(tab.dev), n_desc=tab.rows, src_dtype=_lib.F32,
+             total_blocks=tab.blocks, amax_bits=_p(self._q_amax[slot:]), inv_scale=_p(self._q_inv[slot:]))
 
     def fp8_train_ok(self, x, wnames, geom):
         """Training forward in the fp8 configuration (models.set_compute_dtype('fp8')): the denoiser's 3x3
@@ -887,67 +852,36 @@ class WeightBank:
             out[k] = v
         return out
 
-    def _st_descs(self, units, mats, dst):
-        """numpy descriptor table (SdmiStPackDesc) of one stream: `units` per wave, destination tensor `dst`."""
-        import numpy as np
-        flat = [u for wave in units for u in wave]
-        arr = np.zeros(len(flat), dtype=np.dtype([('src', '<u8'), ('dst', '<u8'), ('rs', '<i4'), ('cs', '<i4')]))
-        base = dst.data_ptr()
-        for i, (key, r0, k0, tr) in enumerate(flat):
-            m = mats[key]
-            ld = m.shape[1]
-            if tr:      # unit rows walk the matrix's columns: element (r, k) = M[k0 + k][r0 + r]
-                arr[i] = (m.data_ptr() + 2 * (k0 * ld + r0), base + i * 2048, 1, ld)
-            else:
-                arr[i] = (m.data_ptr() + 2 * (r0 * ld + k0), base + i * 2048, ld, 1)
-        return arr
-
     ST_STREAMS = ('a', 'b', 'b1', 'b2', 'ba')
 
     def st_train_streams(self, n):
-        """dict(wa, wb, wb1, wb2, wba) -- bf16 unit streams of block `n` for sdmi_st_train_fwd / _bwd.  The streams live in
-        persistent buffers; after an optimiser step (invalidate()) the first request re-packs the streams of ALL
+        """dict(wa, wb, wb1, wb2, wba, C) -- bf16 unit streams of block `n` for sdmi_st_train_fwd / _bwd.  The streams live
+        in persistent buffers; after an optimiser step (invalidate()) the first request re-packs the streams of ALL
         registered blocks with one sdmi_st_pack launch (descriptor table on the device: part of the captured train step)."""
-        if self._stp_stale:
-            self._st_pack_all()
-        ent = self._stp.get(n)
-        if ent is not None and ent['epoch'] == self._stp_epoch and ent['shadow'] == self.model.shadow_arena().data_ptr():
-            return ent
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.SdmiError(f'{n}: first use of a fused training block inside a graph capture (its descriptor '
-                                 'table is a host-to-device copy): run the warm-up passes before capturing')
-        import numpy as np
-        mats = self.st_train_mats(n)
-        C = mats['in'].shape[0]
-        dev = mats['in'].device
-        units = st_train_units(C)
-        if ent is None:
-            ent = {'w' + k: torch.empty((sum(len(w) for w in units[k]) * 1024,), dtype=torch.bfloat16, device=dev)
-                   for k in self.ST_STREAMS}
-        ent['descs'] = np.concatenate([self._st_descs(units[k], mats, ent['w' + k]) for k in self.ST_STREAMS])
-        ent['epoch'], ent['shadow'], ent['C'] = self._stp_epoch, self.model.shadow_arena().data_ptr(), C
-        self._stp[n] = ent
-        self._stp_table = None                      # new member: rebuild the device table at the next re-pack
-        tab = torch.from_numpy(ent['descs'].view(np.uint8).copy()).to(dev)
-        call('sdmi_st_pack', _st(), descs=_p(tab), n_units=len(ent['descs']))
-        ent['_tab'] = tab                            # (kept alive past the launch)
-        return ent
+        m = self.st_streams.get(n)
+        if m is None:
+            mats = self.st_train_mats(n)
+            C = mats['in'].shape[0]
+            dev = mats['in'].device
+            units = st_train_units(C)
+            count = {k: sum(len(w) for w in units[k]) for k in self.ST_STREAMS}
+            st = {'w' + k: torch.empty((count[k] * 1024,), dtype=torch.bfloat16, device=dev) for k in self.ST_STREAMS}
+            descs = np.zeros(sum(count.values()), dtype=self.st_streams.desc)
+            o = 0
+            for k in self.ST_STREAMS:
+                st_pack_descs(descs[o:o + count[k]], units[k], mats, st['w' + k])
+                o += count[k]
+            m = self.st_streams.add(n, SimpleNamespace(streams=dict(st, C=C), descs=descs), dev, rows=len(descs))
+        return m.streams
 
-    def _st_pack_all(self):
-        self._stp_stale = False
-        if not self._stp:
-            return
-        self._stp_epoch += 1
-        if self._stp_table is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.SdmiError('stream descriptor table rebuilt inside a graph capture')
-            import numpy as np
-            arr = np.concatenate([e['descs'] for e in self._stp.values()])
-            dev = next(iter(self._stp.values()))['wa'].device
-            self._stp_table = (torch.from_numpy(arr.view(np.uint8).copy()).to(dev), len(arr))
-        call('sdmi_st_pack', _st(), descs=_p(self._stp_table[0]), n_units=self._stp_table[1])
-        for e in self._stp.values():
-            e['epoch'] = self._stp_epoch
+    @staticmethod
+    def _st_fill(m, rows, blk):
+        rows[:] = m.descs
+        return blk
+
+    @staticmethod
+    def _st_launch(_, tab):
+        call('sdmi_st_pack', _st(), descs=_p(tab.dev), n_units=tab.rows)
 
     def b(self, names):
         """fp32 bias vector, fused across names (view when adjacent)."""
@@ -983,68 +917,56 @@ class WeightBank:
         request re-packs ALL of them with one sdmi_pack_dgrad_batch launch (descriptor table on
         the device) instead of one small launch per layer.  Operands whose forward operand is a
         materialised copy (no fixed arena address) are packed individually."""
-        key = ('dgrad', names if not isinstance(names, str) else (names,), dtype)
-        if self._wd_stale:
-            self._repack_all()
-        ent = self._wd.get(key)
-        if ent is not None and ent[1] == self._wd_epoch:
-            return ent[0]
-        w = self.w(names, dtype)
-        n = w.shape[0]
-        vec = ops.vec_of(dtype)
-        npad = (n + vec - 1) // vec * vec
-        dst = ent[0] if ent is not None else \
-            (torch.zeros if npad != n else torch.empty)((cin_x * kh * kw, npad), dtype=dtype,
-                                                        device=w.device)
-        call('sdmi_pack_dgrad', _st(), src=_p(w), dst=_p(dst), dtype=_DT[dtype], Cout=n, KH=kh,
-             KW=kw, Cin=cin_x, CoutPad=npad)
-        stable = self._in_arena(w)
-        self._wd[key] = [dst, self._wd_epoch, (w if stable else None, n, kh, kw, cin_x, npad)]
-        if stable:
-            self._wd_table = None          # new member: rebuild the descriptor table
-        return dst
-
-    @staticmethod
-    def _fill_desc(d, e, blk):
-        w, n, kh, kw, cin, npad = e[2][:6]
-        d.src, d.dst = w.data_ptr(), e[0].data_ptr()
-        d.Cout, d.KH, d.KW, d.Cin, d.CoutPad, d.block_begin = n, kh, kw, cin, npad, blk
-        taps = kh * kw
-        if len(e[2]) > 6:                       # parity sub-filter: selected taps only
-            d.kh0, d.kw0, d.kstep, d.nkh, d.nkw = e[2][6]
-            taps = d.nkh * d.nkw
-        return blk + taps * ((n + 63) // 64) * ((cin + 63) // 64)
+        return self._dgrad(('dgrad', names if not isinstance(names, str) else (names,), dtype), names, dtype, kh, kw, cin_x)
 
     def wd_sub(self, names, dtype, kh, kw, cin_x, kh0, kw0, step):
         """Parity sub-filter of the dgrad operand (taps kh0::step, kw0::step of the flipped filter,
         [Cin][nkh][nkw][CoutPad]) for the data gradient of a strided convolution; kept and re-packed
         with the other dgrad operands (one sdmi_pack_dgrad_batch launch per optimiser step)."""
         names = names if not isinstance(names, str) else (names,)
-        key = ('dgradsub', names, dtype, kh0, kw0, step)
-        if self._wd_stale:
-            self._repack_all()
-        ent = self._wd.get(key)
-        if ent is not None and ent[1] == self._wd_epoch:
-            return ent[0]
+        sub = (kh0, kw0, step, len(range(kh0, kh, step)), len(range(kw0, kw, step)))
+        return self._dgrad(('dgradsub', names, dtype, kh0, kw0, step), names, dtype, kh, kw, cin_x, sub)
+
+    def _dgrad(self, key, names, dtype, kh, kw, cin_x, sub=None):
+        m = self.dgrad_ops.get(key)
+        if m is not None:
+            return m.dst
         w = self.w(names, dtype)
         n = w.shape[0]
         vec = ops.vec_of(dtype)
         npad = (n + vec - 1) // vec * vec
-        nkh, nkw = len(range(kh0, kh, step)), len(range(kw0, kw, step))
-        dst = ent[0] if ent is not None else \
-            (torch.zeros if npad != n else torch.empty)((cin_x * nkh * nkw, npad), dtype=dtype, device=w.device)
+        taps = kh * kw if sub is None else sub[3] * sub[4]
+        old = self.dgrad_ops.members.get(key)       # (an operand outside the table comes back every epoch: same buffer)
+        dst = old.dst if old is not None else \
+            (torch.zeros if npad != n else torch.empty)((cin_x * taps, npad), dtype=dtype, device=w.device)
         stable = self._in_arena(w)
-        e = [dst, self._wd_epoch, (w if stable else None, n, kh, kw, cin_x, npad, (kh0, kw0, step, nkh, nkw))]
-        # (first use / unstable operand: a one-entry table -- eager only, it copies the table to the device)
-        Desc = _lib.CSTRUCT['SdmiPackDesc']
-        arr = (Desc * 1)()
-        blocks = self._fill_desc(arr[0], [dst, 0, (w,) + e[2][1:]], 0)
-        dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(w.device)
-        call('sdmi_pack_dgrad_batch', _st(), descs=_p(dev), n_desc=1, dtype=_DT[dtype], total_blocks=blocks)
-        self._wd[key] = e
-        if stable:
-            self._wd_table = None
+        m = self.dgrad_ops.add(key, SimpleNamespace(dst=dst, src=w, Cout=n, KH=kh, KW=kw, Cin=cin_x, CoutPad=npad, sub=sub),
+                               w.device, group=dtype, tabled=stable)
+        if not stable:
+            m.src = None                            # a materialised copy: made again, not kept
         return dst
+
+    @staticmethod
+    def _dgrad_fill(m, rows, blk):
+        derived.put(rows, 0, src=m.src.data_ptr(), dst=m.dst.data_ptr(), Cout=m.Cout, KH=m.KH, KW=m.KW, Cin=m.Cin,
+                    CoutPad=m.CoutPad, block_begin=blk)
+        taps = m.KH * m.KW
+        if m.sub is not None:                       # parity sub-filter: selected taps only
+            kh0, kw0, kstep, nkh, nkw = m.sub
+            derived.put(rows, 0, kh0=kh0, kw0=kw0, kstep=kstep, nkh=nkh, nkw=nkw)
+            taps = nkh * nkw
+        return blk + taps * ((m.Cout + 63) // 64) * ((m.Cin + 63) // 64)
+
+    @staticmethod
+    def _dgrad_launch(dtype, tab):
+        call('sdmi_pack_dgrad_batch', _st(), descs=_p(tab.dev), n_desc=tab.rows, dtype=_DT[dtype], total_blocks=tab.blocks)
+
+    def _dgrad_first(self, m, one):
+        if m.sub is None:                           # the plain launch takes no table: legal inside a graph capture
+            call('sdmi_pack_dgrad', _st(), src=_p(m.src), dst=_p(m.dst), dtype=_DT[m.group], Cout=m.Cout, KH=m.KH,
+                 KW=m.KW, Cin=m.Cin, CoutPad=m.CoutPad)
+        else:                                       # (eager only: a one-entry table)
+            self._dgrad_launch(m.group, one())
 
     def _in_arena(self, t):
         m = self.model
@@ -1052,28 +974,6 @@ class WeightBank:
             if a is not None and a.data_ptr() <= t.data_ptr() < a.data_ptr() + a.numel() * a.element_size():
                 return True
         return False
-
-    def _repack_all(self):
-        self._wd_stale = False
-        self._wd_epoch += 1
-        for dtype in {k[2] for k, e in self._wd.items() if e[2][0] is not None}:
-            items = [e for k, e in self._wd.items() if k[2] == dtype and e[2][0] is not None]   # full + sub-filters
-            tab = self._wd_table.get(dtype) if self._wd_table else None
-            if tab is None:
-                Desc = _lib.CSTRUCT['SdmiPackDesc']
-                arr = (Desc * len(items))()
-                blk = 0
-                for d, e in zip(arr, items):
-                    blk = self._fill_desc(d, e, blk)
-                dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(
-                    items[0][0].device)
-                tab = (dev, len(items), blk)
-                self._wd_table = self._wd_table or {}
-                self._wd_table[dtype] = tab
-            call('sdmi_pack_dgrad_batch', _st(), descs=_p(tab[0]), n_desc=tab[1], dtype=_DT[dtype],
-                 total_blocks=tab[2])
-            for e in items:
-                e[1] = self._wd_epoch
 
 
 class Kern:
@@ -1743,7 +1643,6 @@ class GemmFn(torch.autograd.Function):
         # the direct path does: a parameter used several times per step (per-frame modules,
         # gradient accumulation over micro-batches) keeps every contribution
         if not direct:
-            import ctypes
             g = wb.model.grad_arena()
             taps = kh * kw
             o, segs, keep = 0, [], []
@@ -1757,28 +1656,15 @@ class GemmFn(torch.autograd.Function):
                     keep.append(src)
                 segs.append((_p(src), _p(g[off:]), cnt))
                 o += rows
-            Item = _lib.CSTRUCT['SdmiScatterItem']
-            for c0 in range(0, len(segs), 32):         # one launch per 32 destinations
-                chunk = segs[c0:c0 + 32]
-                arr = (Item * len(chunk))()
-                for a_, (sp, dp, cnt) in zip(arr, chunk):
-                    a_.src, a_.dst, a_.count = sp, dp, cnt
-                call('sdmi_scatter_add', _st(), items=ctypes.addressof(arr), n=len(chunk))
+            _scatter_add(segs)
         if stage_bias:
-            import ctypes
             g = wb.model.grad_arena()
             o, segs = 0, []
             for nme in (bnames if not isinstance(bnames, str) else (bnames,)):
                 off, cnt = wb.model._offsets[nme]
                 segs.append((_p(btmp[o:]), _p(g[off:]), cnt))
                 o += cnt
-            Item = _lib.CSTRUCT['SdmiScatterItem']
-            for c0 in range(0, len(segs), 32):
-                chunk = segs[c0:c0 + 32]
-                arr = (Item * len(chunk))()
-                for a_, (sp, dp, cnt) in zip(arr, chunk):
-                    a_.src, a_.dst, a_.count = sp, dp, cnt
-                call('sdmi_scatter_add', _st(), items=ctypes.addressof(arr), n=len(chunk))
+            _scatter_add(segs)
 
 
 class MultiLinearFn(torch.autograd.Function):

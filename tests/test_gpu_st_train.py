@@ -301,3 +301,52 @@ def test_fused_training_block_gradients_match_torch_autograd(name, hw, B, n_slot
     assert errs['out'] < 1e-2
     worst = max(errs, key=errs.get)
     assert errs[worst] < 2e-2, (worst, errs[worst])
+
+
+def test_weight_update_repacks_every_stream_with_one_launch():
+    """After weights_updated() the first fused block of the next pass re-packs the unit streams of ALL registered blocks
+    with ONE sdmi_st_pack over the cached device table (derived.StepTable); every block's streams are then those of the
+    CURRENT shadow weights.  The smallest listed case, and the next one so that the table spans two blocks."""
+    import numpy as np
+    from slotdiffusion_amd import _lib, derived, kern
+    m = _model()
+    KG = m.KG()
+    wb = KG.wb
+    runs = []
+    for name, hw, B, n_slots, rows in sorted(CASES, key=lambda c: c[2] * c[1] * c[1])[:2]:
+        u, n, heads, Cc, x, kv = _inputs(m, name, hw, B, n_slots)
+        runs.append((name, n, heads, x, kv, rows, torch.randn(x.shape, generator=torch.Generator().manual_seed(5)).bfloat16().cuda()))
+
+    def backward_pass():
+        m.grad_arena().zero_()
+        for name, n, heads, x, kv, rows, dout in runs:
+            kern._ST_ROWS = rows
+            xi, kvi = x.clone().requires_grad_(True), kv.clone().requires_grad_(True)
+            out = u._st(KG, name, xi, heads, kvi)
+            assert isinstance(out.grad_fn, kern.StBlockFn._backward_cls), 'the block must take the fused training path'
+            out.backward(dout)
+    old = kern._ST_TRAIN, kern._ST_TRAIN_MIN_WGS, kern._ST_ROWS
+    kern._ST_TRAIN, kern._ST_TRAIN_MIN_WGS = True, 0
+    try:
+        backward_pass()
+        backward_pass()
+        with torch.no_grad():
+            m.arena().mul_(1.25)                   # (the re-packed streams must differ from the kept ones)
+        m.weights_updated()
+        with _lib.KernelTimer() as kt:
+            backward_pass()
+        torch.cuda.synchronize()
+    finally:
+        kern._ST_TRAIN, kern._ST_TRAIN_MIN_WGS, kern._ST_ROWS = old
+    assert sum(1 for r in kt.records if r[0] == 'sdmi_st_pack') == 1
+    assert list(wb.st_streams.members) == [r[1] for r in runs]
+    for _, n, *_ in runs:
+        st = wb.st_train_streams(n)
+        units = kern.st_train_units(st['C'])['a']
+        fresh = torch.zeros_like(st['wa'])
+        rows_ = np.zeros(st['wa'].numel() // 1024, dtype=np.dtype(_lib.CSTRUCT['SdmiStPackDesc']))
+        kern.st_pack_descs(rows_, units, wb.st_train_mats(n), fresh)
+        tab = derived.table_tensor(rows_, 'cuda')
+        _lib.call('sdmi_st_pack', torch.cuda.current_stream().cuda_stream, descs=tab.data_ptr(), n_units=len(rows_))
+        torch.cuda.synchronize()
+        assert torch.equal(st['wa'], fresh), n

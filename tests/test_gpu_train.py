@@ -1156,6 +1156,53 @@ def test_pack_dgrad_batch_matches_single(dtype):
         assert torch.equal(ref, out), shp
 
 
+def test_weight_update_repacks_dgrad_operands_with_one_launch_per_dtype():
+    """After weights_updated() the first data gradient of the next backward pass re-packs every dgrad operand whose
+    source lies in an arena with ONE sdmi_pack_dgrad_batch per compute dtype over the cached device table
+    (derived.StepTable) -- parity sub-filters included; only operands made from a materialised copy are packed one by
+    one.  The kept buffers are then the operands of the CURRENT shadow weights (bit exact)."""
+    from slotdiffusion_amd import _lib
+    from slotdiffusion_amd.kern import _DT
+    G = C.load_golden()
+    img = C.make_inputs(2)[0].cuda()
+    m = _model(torch.bfloat16)
+    _train_backward(m, G, img)
+    _train_backward(m, G, img)
+    with torch.no_grad():
+        m.arena().mul_(1.25)                       # (the re-packed operands must differ from the kept ones)
+    m.weights_updated()
+    with _lib.KernelTimer() as kt:
+        _train_backward(m, G, img)
+    torch.cuda.synchronize()
+    wb = m.bank()
+    members = list(wb.dgrad_ops.members.values())
+    tabled = [x for x in members if x.tabled]
+    launched = [r[0] for r in kt.records]
+    assert len(tabled) >= 30
+    assert launched.count('sdmi_pack_dgrad_batch') == len({x.group for x in tabled})
+    # (the plain launch: only for the operands outside the table, never for one whose source lies in an arena)
+    assert launched.count('sdmi_pack_dgrad') == sum(1 for x in members if not x.tabled and x.sub is None)
+    subs = [x for x in tabled if x.sub is not None]
+    assert subs, 'the model has strided convolutions: their parity sub-filters are table members'
+    st = torch.cuda.current_stream().cuda_stream
+    for x in (tabled[0], tabled[len(tabled) // 2], tabled[-1], subs[0]):
+        src = wb.w(x.key[1], x.group)
+        assert wb._in_arena(src)
+        fresh = torch.zeros_like(x.dst)
+        if x.sub is None:
+            _lib.call('sdmi_pack_dgrad', st, src=src.data_ptr(), dst=fresh.data_ptr(), dtype=_DT[x.group], Cout=x.Cout,
+                      KH=x.KH, KW=x.KW, Cin=x.Cin, CoutPad=x.CoutPad)
+        else:
+            d = _lib.CSTRUCT['SdmiPackDesc'](src=src.data_ptr(), dst=fresh.data_ptr(), Cout=x.Cout, KH=x.KH, KW=x.KW,
+                                             Cin=x.Cin, CoutPad=x.CoutPad)
+            d.kh0, d.kw0, d.kstep, d.nkh, d.nkw = x.sub
+            tab = torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8).cuda()
+            _lib.call('sdmi_pack_dgrad_batch', st, descs=tab.data_ptr(), n_desc=1, dtype=_DT[x.group],
+                      total_blocks=d.nkh * d.nkw * ((x.Cout + 63) // 64) * ((x.Cin + 63) // 64))
+        torch.cuda.synchronize()
+        assert torch.equal(x.dst, fresh), x.key
+
+
 def test_ema_hook_matches_reference_formula():
     """Row a18: LitEma semantics (ddpm/ema.py:29-85) on the flat arena -- decay warm-up
     min(decay, (1+n)/(10+n)), in-place shadow update, ema_scope store / copy_to / restore."""
@@ -1385,7 +1432,8 @@ def test_fp8_train_step_deviation_and_device_scales():
         m.bank().join()
         if mode == 'fp8':
             wb = m.bank()
-            names = sorted(wb._w8, key=lambda n: wb._w8[n][4])
+            ops8 = wb.fp8_ops.members
+            names = sorted(ops8, key=lambda n: ops8[n].slot)
             assert len(names) >= 30
             # every operand: bytes = e4m3fn(w * 448 / amax) of the fp32 master, inv = amax / 448
             for n in names[:4] + names[-2:]:
@@ -1396,7 +1444,7 @@ def test_fp8_train_step_deviation_and_device_scales():
                 ref = ops.quant_fp8(w.contiguous(), float(448.0 / am))
                 assert float((ref != b8).float().mean()) <= 1e-4
             # an optimiser step changes the weights: ONE grouped call re-quantises all of them
-            before = {n: (wb._w8[n][0].clone(), float(wb._w8[n][1])) for n in names[:3]}
+            before = {n: (ops8[n].q.clone(), float(ops8[n].inv)) for n in names[:3]}
             with torch.no_grad():
                 m.arena().mul_(1.25)
             m.weights_updated()
@@ -1405,8 +1453,8 @@ def test_fp8_train_step_deviation_and_device_scales():
                 wb.w8_dev(names[1])
             assert sum(1 for r in kt.records if r[0] == 'sdmi_fp8_quant_group') == 1
             for n in names[:3]:
-                assert abs(float(wb._w8[n][1]) - 1.25 * before[n][1]) <= 1e-5 * before[n][1]
-                assert float((wb._w8[n][0] != before[n][0]).float().mean()) <= 1e-3     # same bytes at 1.25x the scale
+                assert abs(float(ops8[n].inv) - 1.25 * before[n][1]) <= 1e-5 * before[n][1]
+                assert float((ops8[n].q != before[n][0]).float().mean()) <= 1e-3     # same bytes at 1.25x the scale
     R['fp8_eps_rel_l2_vs_bf16'] = float((eps['fp8'] - eps['bf16']).norm() / eps['bf16'].norm())
     R['fp8_eps_rel_l2_vs_ref'] = float((eps['fp8'] - G['eps_pred']).norm() / G['eps_pred'].norm())
     R['bf16_eps_rel_l2_vs_ref'] = float((eps['bf16'] - G['eps_pred']).norm() / G['eps_pred'].norm())
@@ -1426,11 +1474,12 @@ def test_fp8_train_step_deviation_and_device_scales():
     opt = optim.FusedAdam(m, lr=1e-3, dec_lr=1e-3, clip_grad=1.0)
     step = optim.GraphedTrainStep(m, opt, dict(img=img), loss_key='denoise_loss')
     wb = m.bank()
-    name = sorted(wb._w8, key=lambda n: wb._w8[n][4])[0]
+    ops8 = wb.fp8_ops.members
+    name = sorted(ops8, key=lambda n: ops8[n].slot)[0]
     losses, invs = [], []
     for _ in range(4):
         losses.append(float(step(dict(img=img))))
-        invs.append(float(wb._w8[name][1]))
+        invs.append(float(ops8[name].inv))
     torch.cuda.synchronize()
     assert all(math.isfinite(v) for v in losses)
     w = wb._flat(name, torch.float32)

@@ -3,7 +3,7 @@ many runs differ from the first and where (rows / columns) the differing element
 import sys
 import torch
 sys.path.insert(0, '.')
-from slotdiffusion_amd import _lib, kern
+from slotdiffusion_amd import _lib, derived, kern
 
 
 def streams(C, seed=0):
@@ -12,15 +12,16 @@ def streams(C, seed=0):
             dict(po=(C, C), ff2=(C, 4 * C), ff1=(8 * C, C), o2=(C, C), q2=(C, C), o=(C, C), q=(C, C), k=(C, C), v=(C, C),
                  **{'in': (C, C)}).items()}
     units = kern.st_train_units(C)
-    wbk = kern.WeightBank.__new__(kern.WeightBank)
     out = {}
     import numpy as np
     descs = []
     for k in ('b1', 'b2', 'ba'):
-        out[k] = torch.empty(sum(len(w) for w in units[k]) * 1024, dtype=torch.bfloat16, device='cuda')
-        descs.append(kern.WeightBank._st_descs(wbk, units[k], mats, out[k]))
+        n = sum(len(w) for w in units[k])
+        out[k] = torch.empty(n * 1024, dtype=torch.bfloat16, device='cuda')
+        descs.append(np.zeros(n, dtype=np.dtype(_lib.CSTRUCT['SdmiStPackDesc'])))
+        kern.st_pack_descs(descs[-1], units[k], mats, out[k])
     arr = np.concatenate(descs)
-    tab = torch.from_numpy(arr.view(np.uint8).copy()).cuda()
+    tab = derived.table_tensor(arr, 'cuda')
     _lib.call('sdmi_st_pack', torch.cuda.current_stream().cuda_stream, descs=tab.data_ptr(), n_units=len(arr))
     torch.cuda.synchronize()
     return out
