@@ -466,6 +466,62 @@ typedef struct {
 int sdmi_unipc_step(const SdmiUnipcStepArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The image-space twins of the two tails above: the slot-conditioned UNet run directly on [B,3,H,W] images
+ * (CondDDPM, ddpm/cond_ddpm.py), where there is no codebook and the prediction is corrected instead of quantised.
+ * One launch per function evaluation:
+ *   data prediction: exactly sdmi_dpm_step's (targets EPS / X0 / V, the same operations in the same order)
+ *   -> correction of x0 (`correct`):
+ *     SDMI_X0_NONE     none
+ *     SDMI_X0_CLAMP    x0 = clamp(x0, -1, 1)            ancestral / DDIM clip_denoised, cond_ddpm.py:71-72, ddim.py:209-210
+ *     SDMI_X0_DYNAMIC  Imagen's dynamic thresholding, DPM_Solver.dynamic_thresholding_fn, dpm_solver.py:506-515.  A sample
+ *                      is rows_per_sample consecutive rows; over its n = 3 * rows_per_sample values a = |x0|
+ *                        s = quantile(a, p)     torch.quantile's linear interpolation in float32: the host passes the
+ *                                               position as (q_k, q_w), rank = float32(p) * float32(n - 1),
+ *                                               q_k = floor(rank), q_w = rank - q_k; with the order statistics
+ *                                               lo = a_(q_k), hi = a_(q_k + 1) (hi = lo when q_w == 0) and d = hi - lo,
+ *                                               s = q_w < 0.5 ? fma(q_w, d, lo) : fma(-d, 1 - q_w, hi)  (ATen's lerp,
+ *                                               which rounds once: probed against torch on the CPU and on the device)
+ *                        s = max(s, max_val);   x0 = clamp(x0, -s, s) / s     (IEEE division)
+ *                      A NaN anywhere in a sample makes its s and its whole corrected prediction NaN (as
+ *                      torch.quantile followed by torch.clamp does); other samples are untouched.
+ *   -> m0 (the corrected prediction, kept as solver history)
+ *   -> the update: SDMI_DPM_UPD_* of sdmi_dpm_step, or sdmi_unipc_step's corrector + predictor (orders 0..3), with the same
+ *      operands and coefficient meanings, from the corrected prediction.
+ * The chain that gives the same bits: sdmi_lincomb (data prediction), torch abs / quantile / maximum / clamp / div on the
+ * first three channels (slotdiffusion_amd.ops.thresh_chain spells it), the sdmi_lincomb updates listed above.
+ * x, base, h1.., m0, xc, y are [R][4] fp32 rows (16-byte aligned; pad channel written 0); only the first 3 channels of
+ * `out` are read.  DYNAMIC runs one workgroup per sample with the sample's prediction held in registers and finds the two
+ * order statistics by a radix select over the bit patterns of |x0| (no sort; |x0| never goes to memory); it serves
+ * rows_per_sample <= SDMI_PX_MAX_ROWS (128 x 128).  Refused before any launch: null pointers for the streams read or
+ * written, unknown target / update form / correction, orders outside 0..3, rows_per_sample <= 0, R not a multiple of
+ * rows_per_sample, for DYNAMIC q_k outside [0, n - 1], q_w outside [0, 1) or non-zero at q_k = n - 1, max_val not
+ * positive, and any output that overlaps an input or another output (SDMI_EINVAL); DYNAMIC with rows_per_sample >
+ * SDMI_PX_MAX_ROWS returns SDMI_EUNSUPPORTED, and the caller runs the chain.
+ * ------------------------------------------------------------------------------------------ */
+enum { SDMI_X0_NONE = 0, SDMI_X0_CLAMP = 1, SDMI_X0_DYNAMIC = 2 };
+enum { SDMI_PX_MAX_ROWS = 16384 };
+typedef struct {
+  const float* x; const float* out; float* m0;
+  const float* base; const float* h1; const float* h2; float* y;
+  int R, rows_per_sample, target, mode, correct, q_k;
+  float q_w, max_val, sigma, alpha;
+  float c0, c1, c2, c3, k0, k1, g, k2;
+} SdmiDpmStepPxArgs;
+int sdmi_dpm_step_px(const SdmiDpmStepPxArgs* a, void* stream);
+
+typedef struct {
+  const float* x; const float* out; float* m0;
+  int R, rows_per_sample, target, correct, q_k;
+  float q_w, max_val, sigma, alpha;
+  const float* base; const float* h1; const float* h2; const float* h3;
+  float* xc; float* y;
+  int corr_order, pred_order;
+  float c0, c1, w1, w2, wn;
+  float p0, p1, q1, q2;
+} SdmiUnipcStepPxArgs;
+int sdmi_unipc_step_px(const SdmiUnipcStepPxArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Small fused elementwise kernels.
  * ------------------------------------------------------------------------------------------ */
 /* y = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div   (fp32; NULL operands skipped, x3 NULL -> c2*x2,

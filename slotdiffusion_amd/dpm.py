@@ -80,16 +80,26 @@ UPD_NONE, UPD_FIRST, UPD_SINGLE, UPD_MULTI2, UPD_MULTI3 = 0, 1, 2, 3, 4
 
 
 def check_options(method='singlestep', order=3, skip_type='time_uniform', solver_type='dpmsolver',
-                  algorithm_type='dpmsolver++', correcting_x0_fn=None, guidance_scale=1.):
-    """ValueError for everything of DPM_Solver.sample / model_wrapper this sampler does not build."""
+                  algorithm_type='dpmsolver++', correcting_x0_fn=None, guidance_scale=1., vq_denoised=True,
+                  dynamic_thresholding_ratio=0.995, thresholding_max_val=1.0):
+    """ValueError for everything of DPM_Solver.sample / model_wrapper this sampler does not build.  correcting_x0_fn
+    (dynamic thresholding) belongs to the image-space decoder: with vq_denoised (the latent decoder, the default) it is
+    refused, as the reference refuses the pair (dpm_solver.py:503-504)."""
     if method not in METHODS:
         raise ValueError(f"method={method!r}: built are {METHODS} ('adaptive' needs a host decision per step)")
     if solver_type != 'dpmsolver':
         raise ValueError(f"solver_type={solver_type!r}: only 'dpmsolver' is built")
     if algorithm_type != 'dpmsolver++':
         raise ValueError(f"algorithm_type={algorithm_type!r}: only 'dpmsolver++' (data prediction) is built")
-    if correcting_x0_fn:
-        raise ValueError(f'correcting_x0_fn={correcting_x0_fn!r}: dynamic thresholding is not built')
+    if correcting_x0_fn and vq_denoised:
+        raise ValueError(f'correcting_x0_fn={correcting_x0_fn!r}: dynamic thresholding is for the image-space decoder; '
+                         'the latent decoder quantises its prediction instead (vq_denoised)')
+    if correcting_x0_fn not in (None, False, True, 'dynamic_thresholding'):
+        raise ValueError(f"correcting_x0_fn={correcting_x0_fn!r}: only 'dynamic_thresholding' is built")
+    if not 0. < float(dynamic_thresholding_ratio) <= 1.:
+        raise ValueError(f'dynamic_thresholding_ratio={dynamic_thresholding_ratio!r}: must be in (0, 1]')
+    if not float(thresholding_max_val) > 0.:
+        raise ValueError(f'thresholding_max_val={thresholding_max_val!r}: must be positive')
     if guidance_scale != 1.:
         raise ValueError(f'guidance_scale={guidance_scale!r}: only 1 (no classifier-free guidance) is built')
     if order not in (1, 2, 3):
@@ -338,6 +348,16 @@ def plan_key(steps=20, order=3, method='singlestep', skip_type='time_uniform', t
     return (int(steps), int(order), str(method), str(skip_type),
             None if t_start is None else float(t_start), None if t_end is None else float(t_end),
             bool(lower_order_final), bool(denoise_to_zero))
+
+
+def correct_key(clip_denoised, correcting_x0_fn=None, dynamic_thresholding_ratio=0.995, thresholding_max_val=1.0):
+    """The correction of x0 an image-space solver call applies, as the extra element of its HIP-graph cache key (the
+    time grid does not depend on it, so plan_key does not hold it): ('dynamic', ratio, max_val) when the keyword asks
+    for thresholding or -- for False / None, as CondDDPM.generate_imgs passes clip_denoised there (cond_ddpm.py:174-180)
+    -- the decoder clips; otherwise ('none', 0., 0.)."""
+    if correcting_x0_fn or clip_denoised:
+        return ('dynamic', float(dynamic_thresholding_ratio), float(thresholding_max_val))
+    return ('none', 0., 0.)
 
 
 def plan_from_key(betas, key):

@@ -12,6 +12,7 @@ inside, everything is NHWC in the compute dtype (fp32 for parity runs, bf16 for 
 """
 import contextlib
 import copy
+import functools
 import os
 
 import torch
@@ -232,7 +233,8 @@ class LDM(_Owned):
         'time_uniform' | 'logSNR' | 'time_quadratic', t_start / t_end (x_T is then the state AT t_start: see
         noise_latent), denoise_to_zero, lower_order_final.  Not built, and refused with a ValueError naming the
         argument: dpm_method='adaptive', dpm_solver_type='taylor', dpm_algorithm_type='dpmsolver',
-        dpm_correcting_x0_fn (dynamic thresholding), guidance_scale != 1.  With ret_intermed the second result is the
+        dpm_correcting_x0_fn (dynamic thresholding) on this latent decoder -- the image-space CondDDPM builds it --,
+        guidance_scale != 1.  With ret_intermed the second result is the
         reference's `intermediates`: one state per outer step (singlestep), the initial state and one per step
         (multistep), then the denoise_to_zero state when asked.
 
@@ -249,13 +251,17 @@ class LDM(_Owned):
                                 solver_type=kwargs.get('unipc_solver_type', 'dpmsolver'),
                                 algorithm_type=kwargs.get('unipc_algorithm_type', 'dpmsolver++'),
                                 correcting_x0_fn=kwargs.get('unipc_correcting_x0_fn'),
-                                guidance_scale=kwargs.get('guidance_scale', 1.))
+                                guidance_scale=kwargs.get('guidance_scale', 1.), vq_denoised=self.vq_denoised,
+                                dynamic_thresholding_ratio=kwargs.get('unipc_dynamic_thresholding_ratio', 0.995),
+                                thresholding_max_val=kwargs.get('unipc_thresholding_max_val', 1.0))
         elif use_dpm:
             dpm.check_options(method=dpm_method, order=dpm_order, skip_type=dpm_skip_type,
                               solver_type=kwargs.get('dpm_solver_type', 'dpmsolver'),
                               algorithm_type=kwargs.get('dpm_algorithm_type', 'dpmsolver++'),
                               correcting_x0_fn=kwargs.get('dpm_correcting_x0_fn'),
-                              guidance_scale=kwargs.get('guidance_scale', 1.))
+                              guidance_scale=kwargs.get('guidance_scale', 1.), vq_denoised=self.vq_denoised,
+                              dynamic_thresholding_ratio=kwargs.get('dpm_dynamic_thresholding_ratio', 0.995),
+                              thresholding_max_val=kwargs.get('dpm_thresholding_max_val', 1.0))
         if cond.dim() == 2:
             cond = cond.unsqueeze(0).expand(batch_size, -1, -1)
         cond = cond.contiguous()
@@ -270,11 +276,12 @@ class LDM(_Owned):
             x, inter = r._unipc_sample(x, cond, ret_intermed, steps=unipc_steps, order=unipc_order, variant=unipc_variant,
                                        skip_type=unipc_skip_type, t_start=unipc_t_start, t_end=unipc_t_end,
                                        lower_order_final=unipc_lower_order_final, corrector=unipc_corrector,
-                                       denoise_to_zero=unipc_denoise_to_zero)
+                                       denoise_to_zero=unipc_denoise_to_zero, correct=self._x0_correction('unipc_', kwargs))
         elif use_dpm:          # cond_ddpm.py:155-178 (takes precedence, as in the reference)
             x, inter = r._dpm_sample(x, cond, ret_intermed, steps=dpm_steps, order=dpm_order, method=dpm_method,
                                      skip_type=dpm_skip_type, t_start=dpm_t_start, t_end=dpm_t_end,
-                                     denoise_to_zero=dpm_denoise_to_zero, lower_order_final=dpm_lower_order_final)
+                                     denoise_to_zero=dpm_denoise_to_zero, lower_order_final=dpm_lower_order_final,
+                                     correct=self._x0_correction('dpm_', kwargs))
         elif use_ddim:         # cond_ddpm.py:180-190: DDIM, max(200, T // 5) steps, eta = 0
             steps = kwargs.get('ddim_steps') or max(200, self.num_timesteps // 5)
             x, inter = r._ddim_sample(x, cond, steps, kwargs.get('eta', 0.), ret_intermed,
@@ -285,6 +292,11 @@ class LDM(_Owned):
         if ret_intermed:
             return out, torch.stack([ops.nhwc_to_nchw(i, 3) for i in inter], 0)
         return out
+
+    def _x0_correction(self, prefix, kwargs):
+        """The extra element of an image-space solver call's cache key (dpm.correct_key); None on the latent decoder,
+        whose prediction is quantised."""
+        return None
 
     @torch.no_grad()
     def noise_latent(self, z0, t, noise=None):
@@ -304,6 +316,55 @@ class LDM(_Owned):
         B = cond.shape[0]
         ret = self.generate_imgs(cond=cond, batch_size=B, ret_intermed=False, **kwargs)
         return {'samples': self.vae.decode(ret)}
+
+
+class CondDDPM(LDM):
+    """`model.dm_decoder` of a dec_dict without `vae_dict` (cond_ddpm.py:21-240): the same slot-conditioned UNet run
+    directly on [B,3,H,W] images.  There is no VAE: x0 is the image itself, the sampled state is the image, and the data
+    prediction is corrected instead of quantised -- Imagen's dynamic thresholding in the DPM-Solver++ family (one
+    sdmi_dpm_step_px / sdmi_unipc_step_px launch per evaluation), a clamp to [-1, 1] in the ancestral and DDIM samplers.
+    New keywords of generate_imgs: dpm_dynamic_thresholding_ratio=0.995, dpm_thresholding_max_val=1.0 and their unipc_
+    twins; dpm_correcting_x0_fn='dynamic_thresholding' | True asks for thresholding, False / None follows clip_denoised
+    (as the reference passes it: cond_ddpm.py:174-180).  Samples of more than ops.PX_MAX_ROWS pixels (128 x 128) take the
+    composed thresholding chain instead of the fused launch, and such a sampler call is NOT captured into a HIP graph:
+    its whole loop, UNet included, is issued eagerly at every call (SADiffusion._solver_sample)."""
+    clip_denoised = True
+    vq_denoised = False
+
+    def encode_x0(self, img):
+        """x0 is the image: [B,3,H,W] -> NHWC-4 fp32 rows (cond_ddpm.py:216; no encode, no z_scale_factor)."""
+        with torch.no_grad():
+            return ops.nchw_to_nhwc(img.float(), torch.float32, 4)
+
+    def _x0_correction(self, prefix, kwargs):
+        return dpm.correct_key(self.clip_denoised, kwargs.get(prefix + 'correcting_x0_fn'),
+                               kwargs.get(prefix + 'dynamic_thresholding_ratio', 0.995),
+                               kwargs.get(prefix + 'thresholding_max_val', 1.0))
+
+    @torch.no_grad()
+    def log_images(self, batch, ret_intermed=False, **kwargs):
+        """cond_ddpm.py:217-262 with ret_intermed=False (grids need torchvision, out of scope): the sampled state is the
+        image, NCHW."""
+        if ret_intermed:
+            raise ValueError('ret_intermed=True: the diffusion / denoise rows of log_images are torchvision grids, not built')
+        cond = batch[self.cond_stage_key]
+        return {'samples': self.generate_imgs(cond=cond, batch_size=cond.shape[0], ret_intermed=False, **kwargs)}
+
+
+def _decoder_nodes(dec_dict, who):
+    """node classes of `dm_decoder`, chosen as the reference chooses (sa_diffusion.py:141-148: a truthy `vae_dict` makes
+    it the LDM), and the refusals of what the image-space decoder does not build."""
+    if dec_dict.get('vae_dict'):
+        return {'dm_decoder': LDM, 'dm_decoder.vae': VQVAEWrapper}
+    if who == 'LDMSlotFormer':
+        raise ValueError("LDMSlotFormer over an image-space decoder (dec_dict without vae_dict) is not built")
+    ud = dec_dict['unet_dict']
+    for k in ('in_channels', 'out_channels'):
+        if ud.get(k, 3) != 3:
+            raise ValueError(f"unet_dict[{k!r}]={ud[k]!r}: the image-space decoder is built for 3 channels")
+    if dec_dict.get('conditioning_key', 'crossattn') != 'crossattn':
+        raise ValueError(f"conditioning_key={dec_dict['conditioning_key']!r}: only 'crossattn' is built")
+    return {'dm_decoder': CondDDPM}
 
 
 class SlotModelBase(FlatModule):
@@ -402,7 +463,7 @@ class _Evaluator:
     def __init__(self, model, cond, times=None, zero_pad=True):
         self.model, self.unet, self.K, self.zero_pad = model, model.unet(), model.K(), zero_pad
         self.ctx_kv = self.unet.context_kv(self.K, model._ctx(cond))
-        self.code = model.bank().f(model.vq_key)
+        self.code = model.bank().f(model.vq_key) if model.vq_key else None
         self.target = model.dm_decoder.pred_target
         self.device = cond.device
         if times is not None:
@@ -421,7 +482,9 @@ class _Evaluator:
 
 
 class SADiffusion(SlotModelBase):
-    """SlotDiffusion on images (registry name 'SADiffusion')."""
+    """SlotDiffusion on images (registry name 'SADiffusion'): the latent decoder (LDM) for a dec_dict with a `vae_dict`,
+    the image-space decoder (CondDDPM) without one."""
+    fused_px = True        # False: the image-space tails run the composed chain (ops.thresh_chain), the tests' yardstick
 
     def __init__(self, resolution, slot_dict, enc_dict, dec_dict, loss_dict=None, eps=1e-6,
                  compute_dtype=None, seed=0):
@@ -430,8 +493,8 @@ class SADiffusion(SlotModelBase):
         sp = self._make_spec(resolution, slot_dict, enc_dict, dec_dict)
         sched = {k: dd[k] for k in ('timesteps', 'beta_schedule', 'linear_start', 'linear_end')
                  if k in dd}
-        super().__init__(sp, schedule_kwargs=sched, seed=seed,
-                         node_classes={'dm_decoder': LDM, 'dm_decoder.vae': VQVAEWrapper})
+        nodes = _decoder_nodes(dec_dict, type(self).__name__)
+        super().__init__(sp, schedule_kwargs=sched, seed=seed, node_classes=nodes)
         assert dd.get('pred_target', 'eps') in ('eps', 'x0', 'v')     # video_based ddpm.py:79
         self.dm_decoder.pred_target = dd.get('pred_target', 'eps')
         self.resolution = tuple(resolution)
@@ -443,16 +506,18 @@ class SADiffusion(SlotModelBase):
         self.num_iterations = slot_dict['num_iterations']
         self.rplan, self.visual_resolution = spec.encoder_plan(self.resolution, enc_dict)
         self.latent_res = tuple(dec_dict['resolution'])
-        self.ed = dec_dict['vae_dict']['enc_dec_dict']
-        self.z_scale = float(dd.get('z_scale_factor', 1.))
-        self.vq_key = 'dm_decoder.vae.vqvae.quantize.embedding.weight'
+        self.pixel = 'dm_decoder.vae' not in nodes                # image-space decoder: no VAE, no codebook
+        self.ed = None if self.pixel else dec_dict['vae_dict']['enc_dec_dict']
+        self.z_scale = 1. if self.pixel else float(dd.get('z_scale_factor', 1.))
+        self.vq_key = None if self.pixel else 'dm_decoder.vae.vqvae.quantize.embedding.weight'
         self.unet_cfg = dec_dict['unet_dict']
         self.testing = False
         # ResBlock dropout (unet_dict['dropout']); parity tests switch it off (RNG streams differ)
         self.train_dropout = float(dec_dict['unet_dict'].get('dropout', 0.0))
         self.compute_dtype = compute_dtype or default_compute_dtype()
         self.dm_decoder._bind(self)
-        self.dm_decoder.vae._bind(self)
+        if not self.pixel:
+            self.dm_decoder.vae._bind(self)
         self._bank = None
         self._unet = None
         self._plans = {}           # dpm.plan_key / unipc.plan_key -> (plan, model times on the device, program)
@@ -510,11 +575,19 @@ class SADiffusion(SlotModelBase):
     def _solver_sample(self, mod, loop, x, cond, ret_intermed, steps, solver):
         """loop(x, cond, prep, ret_intermed) -> (x_0, intermediates) for the configuration `solver` of mod (dpm or unipc),
         eagerly -- or, with use_graph and no intermediates asked, from the HIP graph captured once per (batch,
-        mod.plan_key, condition shape)."""
+        mod.plan_key, condition shape).  `correct` (image-space decoder: dpm.correct_key) is not part of the plan -- the
+        time grid does not depend on it -- and extends the graph key by one element."""
+        correct = solver.pop('correct', None)
+        if correct is not None:
+            loop = functools.partial(loop, correct=correct)
         cfg = mod.plan_key(steps or max(20, self.dm_decoder.num_timesteps // 50), **solver)
-        if ret_intermed or not self.use_graph:
+        # the composed thresholding chain (samples past the fused tail's size) is never captured: a replay of a graph
+        # holding it faulted once (cause not established), so such a call runs its whole loop eagerly, UNet included
+        chain = correct is not None and correct[0] == 'dynamic' and \
+            (not self.fused_px or x.shape[1] * x.shape[2] > ops.PX_MAX_ROWS)
+        if ret_intermed or not self.use_graph or chain:
             return loop(x, cond, self._prepare(mod, cfg, x.device), ret_intermed)
-        key = (x.shape[0], cfg, tuple(cond.shape))
+        key = (x.shape[0], cfg, tuple(cond.shape)) + (() if correct is None else (correct,))
         g = self._graph_cache.get(key)
         if g is None:
             prep = self._prepare(mod, cfg, x.device)
@@ -537,14 +610,15 @@ class SADiffusion(SlotModelBase):
         return out, []
 
     @staticmethod
-    def dpm_cache_key(batch, cond_shape, steps=20, **solver):
-        """Key of the HIP-graph cache entry of one sampler call: batch, the full solver configuration, condition shape."""
-        return (batch, dpm.plan_key(steps, **solver), tuple(cond_shape))
+    def dpm_cache_key(batch, cond_shape, steps=20, correct=None, **solver):
+        """Key of the HIP-graph cache entry of one sampler call: batch, the full solver configuration, condition shape --
+        and, on the image-space decoder, the correction of x0 (dpm.correct_key) as a fourth element."""
+        return (batch, dpm.plan_key(steps, **solver), tuple(cond_shape)) + (() if correct is None else (tuple(correct),))
 
     @staticmethod
-    def unipc_cache_key(batch, cond_shape, steps=20, **solver):
+    def unipc_cache_key(batch, cond_shape, steps=20, correct=None, **solver):
         """Key of the HIP-graph cache entry of one UniPC sampler call (never equal to a dpm_cache_key)."""
-        return (batch, unipc.plan_key(steps, **solver), tuple(cond_shape))
+        return (batch, unipc.plan_key(steps, **solver), tuple(cond_shape)) + (() if correct is None else (tuple(correct),))
 
     def _prepare(self, mod, cfg, device):
         """cfg (mod.plan_key, mod = dpm or unipc) -> (plan, model times of its evaluations on the device, flat program);
@@ -556,20 +630,26 @@ class SADiffusion(SlotModelBase):
             ent = self._plans[(cfg, device)] = (plan, tin, mod.program(plan))
         return ent
 
-    def _dpm_tail_loop(self, x, cond, prep, ret_intermed):
+    def _dpm_tail_loop(self, x, cond, prep, ret_intermed, correct=None):
         """Per function evaluation the UNet and ONE sdmi_dpm_step launch (data prediction for the model's target, VQ,
-        solver update), driven by dpm.run_program."""
+        solver update), driven by dpm.run_program.  On the image-space decoder the launch is sdmi_dpm_step_px: the
+        correction `correct` = (mode, ratio, max_val) in the place of the VQ."""
         plan, tin, prog = prep
         ev = self._evaluator(cond, tin, zero_pad=False)                    # (the pad channel is never read)
+        if self.pixel and correct is None:
+            correct = dpm.correct_key(self.dm_decoder.clip_denoised)
 
         def tail(xc, e, upd, base, h1, h2):
+            if self.pixel:
+                return ops.dpm_step_px(xc, ev(xc), e, target=ev.target, correct=correct[0], ratio=correct[1],
+                                       max_val=correct[2], upd=upd, base=base, h1=h1, h2=h2, fused=self.fused_px)
             return ops.dpm_step(xc, ev(xc), ev.code, e, scale=self.z_scale, target=ev.target, upd=upd, base=base, h1=h1,
                                 h2=h2)[:2]
 
         x, inter = dpm.run_program(prog, x, tail, emit_initial=plan.get('method') == 'multistep')
         return x, (inter if ret_intermed else [])
 
-    def _unipc_loop(self, x, cond, prep, ret_intermed):
+    def _unipc_loop(self, x, cond, prep, ret_intermed, correct=None):
         """Per function evaluation the UNet and ONE sdmi_unipc_step launch (data prediction for the model's target, VQ,
         the corrector of the step just taken, the predictor of the next), driven by unipc.run_program.  The solver
         state stays fp32 in every compute dtype.  The predictions rotate through four buffers (the newest and the three
@@ -580,9 +660,16 @@ class SADiffusion(SlotModelBase):
         hist = [torch.empty_like(x) for _ in range(4)]
         xcs = [torch.empty_like(x) for _ in range(2)]
         ys = [torch.empty_like(x) for _ in range(2)]
+        if self.pixel and correct is None:
+            correct = dpm.correct_key(self.dm_decoder.clip_denoised)
 
         def tail(xe, rec, base, h1, h2, h3):
             n = ev.n
+            if self.pixel:                                                 # sdmi_unipc_step_px: correction, no VQ
+                return ops.unipc_step_px(xe, ev(xe), rec, target=ev.target, correct=correct[0], ratio=correct[1],
+                                         max_val=correct[2], base=base, h1=h1, h2=h2, h3=h3, m0=hist[n % 4],
+                                         xc=None if ret_intermed else xcs[n % 2], y=None if ret_intermed else ys[n % 2],
+                                         fused=self.fused_px)
             return ops.unipc_step(xe, ev(xe), ev.code, rec, scale=self.z_scale, target=ev.target, base=base, h1=h1, h2=h2,
                                   h3=h3, m0=hist[n % 4], xc=None if ret_intermed else xcs[n % 2],
                                   y=None if ret_intermed else ys[n % 2])[:3]
@@ -634,7 +721,7 @@ class SADiffusion(SlotModelBase):
                                  -float(tab['sqrt_one_minus_alphas_bar'][t]), out)
             else:
                 x0 = out
-            x0 = ops.vq_nearest(x0, ev.code, scale=self.z_scale, want_idx=False)[1]
+            x0 = self._denoise_x0(x0, ev)
             x = ops.lincomb(float(tab['posterior_mean_coef1'][t]), x0,
                             float(tab['posterior_mean_coef2'][t]), x)
             if t != 0:
@@ -645,6 +732,16 @@ class SADiffusion(SlotModelBase):
                 x = ops.lincomb(1.0, x, sd, nz)
             yield x, t
 
+    def _denoise_x0(self, x0, ev):
+        """The ancestral sampler's treatment of its predicted x0 (cond_ddpm.py:70-75): the VQ of the latent decoder, or
+        the image-space decoder's clamp to [-1, 1] -- sdmi_dpm_step_px without an update on (x, out) = (x0, x0) at
+        sigma = 0, alpha = 1, whose data prediction (1 * x0 + (-0) * x0) / 1 is x0 itself."""
+        if not self.pixel:
+            return ops.vq_nearest(x0, ev.code, scale=self.z_scale, want_idx=False)[1]
+        if not self.dm_decoder.clip_denoised:
+            return x0
+        return ops.dpm_step_px(x0, x0, dict(sigma=0., alpha=1.), target='eps', correct='clamp')[0]
+
     def _ddim_steps(self, x, cond, plan):
         """Generator over the DDIM updates of `plan` (a list of dpm.ddim_plan entries, any subset in
         sampling order): yields (x after the step, step)."""
@@ -653,8 +750,12 @@ class SADiffusion(SlotModelBase):
         B = x.shape[0]
         for st in plan:
             eps = ev(x)
-            x0 = ops.lincomb(1.0, x, -st['som'], eps, div=st['sqrt_a'])
-            x0 = ops.vq_nearest(x0, ev.code, scale=self.z_scale, want_idx=False)[1]
+            if self.pixel:     # the same operations in the same order, and the clamp, in ONE sdmi_dpm_step_px launch
+                x0 = ops.dpm_step_px(x, eps, dict(sigma=st['som'], alpha=st['sqrt_a']), target='eps',
+                                     correct='clamp' if self.dm_decoder.clip_denoised else 'none')[0]
+            else:
+                x0 = ops.lincomb(1.0, x, -st['som'], eps, div=st['sqrt_a'])
+                x0 = ops.vq_nearest(x0, ev.code, scale=self.z_scale, want_idx=False)[1]
             x = ops.lincomb(st['sqrt_a_prev'], x0, st['dir'], eps)
             if st['sigma'] != 0.0:
                 nz = ops.nchw_to_nhwc(torch.randn(B, 3, x.shape[1], x.shape[2], device=x.device),
@@ -1080,10 +1181,12 @@ class LDMSlotFormer(SADiffusion):
         dec_dict = copy.deepcopy(dec_dict)
         weight_path = dec_dict.pop('dec_ckp_path', '')
         dd = dec_dict['diffusion_dict']
+        _decoder_nodes(dec_dict, 'LDMSlotFormer')                     # (refuses an image-space decoder by name)
         sp = spec.ldm_slotformer(slot_dict, dec_dict, rollout_dict)
         sched = {k: dd[k] for k in ('timesteps', 'beta_schedule', 'linear_start', 'linear_end') if k in dd}
         FlatModule.__init__(self, sp, schedule_kwargs=sched, seed=seed,
                             node_classes={'dm_decoder': LDM, 'dm_decoder.vae': VQVAEWrapper})
+        self.pixel = False
         assert dd.get('pred_target', 'eps') in ('eps', 'x0', 'v')
         self.dm_decoder.pred_target = dd.get('pred_target', 'eps')
         self.resolution, self.clip_len, self.eps = tuple(resolution), clip_len, eps

@@ -537,6 +537,157 @@ def unipc_step(x, out, codebook, rec, *, scale=1.0, target='eps', base=None, h1=
     return m0, xc, y, idx
 
 
+_X0_CORRECT = {None: 0, 'none': 0, 'clamp': 1, 'dynamic': 2}     # sdmi.h: SDMI_X0_NONE / _CLAMP / _DYNAMIC
+PX_MAX_ROWS = _lib.ENUMS['SDMI_PX_MAX_ROWS']
+
+
+def quantile_rank(n, q):
+    """Position of torch.quantile(., q) (linear interpolation) in a sorted row of n float32 values, derived in float32
+    the way ATen does (q cast to float32, times n - 1, floor) -> (k, w): the lower rank and the interpolation weight."""
+    import numpy as np
+    rank = np.float32(q) * np.float32(n - 1)
+    k = int(np.floor(rank))
+    return k, float(np.float32(rank - np.float32(k)))
+
+
+def _px_common(x, out, correct, ratio, max_val):
+    """The fields the two image-space tails share: shape, correction mode and the quantile position of one sample."""
+    assert x.dim() >= 2 and x.shape[-1] == 4 and out.shape == x.shape
+    R = x.numel() // 4
+    rps = R // x.shape[0]
+    kw = dict(R=R, rows_per_sample=rps, correct=_X0_CORRECT[correct])
+    if correct == 'dynamic':
+        k, w = quantile_rank(3 * rps, ratio)
+        kw.update(q_k=k, q_w=w, max_val=float(max_val))
+    return kw
+
+
+def thresh_chain(x, out, e, *, target='eps', correct='dynamic', ratio=0.995, max_val=1.0):
+    """The corrected data prediction of an image-space model, composed: the sdmi_lincomb data prediction of
+    ops.dpm_step's chain, then on the three real channels torch abs / quantile / maximum / clamp / div exactly as
+    DPM_Solver.dynamic_thresholding_fn spells them (dpm_solver.py:506-515; 'clamp': clamp_(-1, 1), cond_ddpm.py:71-72),
+    pad channel 0.  x, out [B, ..., 4] fp32; a sample is one entry of dim 0.  The fallback of the fused tails past their
+    sample size, and the yardstick of their tests."""
+    if target == 'x0':
+        eps = lincomb(1.0, x, -e['alpha'], out, div=e['sigma'])
+    elif target == 'v':
+        eps = lincomb(e['alpha'], out, e['sigma'], x)
+    else:
+        eps = out
+    x0 = lincomb(1.0, x, -e['sigma'], eps, div=e['alpha'])
+    m0 = torch.zeros_like(x0)
+    c = x0[..., :3]
+    if correct == 'clamp':
+        c = c.clamp(-1., 1.)
+    elif correct == 'dynamic':
+        B = c.shape[0]
+        s = torch.quantile(torch.abs(c).reshape((B, -1)), ratio, dim=1)
+        s = torch.maximum(s, max_val * torch.ones_like(s)).view((B,) + (1,) * (c.dim() - 1))
+        c = torch.clamp(c, -s, s) / s
+    else:
+        assert correct in (None, 'none')
+    m0[..., :3] = c
+    return m0
+
+
+def dpm_update_chain(upd, base, m0, h1=None, h2=None):
+    """The DPM-Solver++ update of sdmi.h's SDMI_DPM_UPD_* as the sdmi_lincomb launches that give the same bits."""
+    u = upd
+    if u['mode'] == 1:
+        return lincomb(u['c0'], base, u['c1'], m0)
+    if u['mode'] == 2:
+        return lincomb(u['c0'], base, u['c1'], h1, u['c2'], m0, h1)
+    D1_0 = lincomb(c2=u['k0'], x2=m0, x3=h1)
+    if u['mode'] == 3:
+        return lincomb(u['c0'], base, u['c1'], m0, u['c2'], D1_0)
+    D1_1 = lincomb(c2=u['k1'], x2=h1, x3=h2)
+    D1 = lincomb(1.0, D1_0, c2=u['g'], x2=D1_0, x3=D1_1)
+    D2 = lincomb(c2=u['k2'], x2=D1_0, x3=D1_1)
+    y1 = lincomb(u['c0'], base, u['c1'], m0, u['c2'], D1)
+    return lincomb(1.0, y1, u['c3'], D2)
+
+
+def unipc_update_chain(rec, base, m0, h1=None, h2=None, h3=None, xc=None, y=None):
+    """UniPC's corrector and predictor (sdmi.h: sdmi_unipc_step) as sdmi_lincomb launches -> (xc or None, y or None)."""
+    c, p = rec['corr'], rec['pred']
+    if c is not None:
+        v = lincomb(c['c0'], base, c['c1'], h1, c['w1'], h2, h1) if c['order'] >= 2 else \
+            lincomb(c['c0'], base, c['c1'], h1)
+        if c['order'] == 3:
+            v = lincomb(1.0, v, c2=c['w2'], x2=h3, x3=h1)
+        xc = lincomb(1.0, v, c2=c['wn'], x2=m0, x3=h1, out=xc)
+    else:
+        xc = None
+    if p is not None:
+        s = base if xc is None else xc
+        if p['order'] == 3:
+            v = lincomb(p['c0'], s, p['c1'], m0, p['q1'], h1, m0)
+            y = lincomb(1.0, v, c2=p['q2'], x2=h2, x3=m0, out=y)
+        elif p['order'] == 2:
+            y = lincomb(p['c0'], s, p['c1'], m0, p['q1'], h1, m0, out=y)
+        else:
+            y = lincomb(p['c0'], s, p['c1'], m0, out=y)
+    else:
+        y = None
+    return xc, y
+
+
+def dpm_step_px(x, out, e, *, target='eps', correct='dynamic', ratio=0.995, max_val=1.0, upd=None, base=None, h1=None,
+                h2=None, fused=True):
+    """One function evaluation's tail of an image-space model in one launch (sdmi.h: sdmi_dpm_step_px): data prediction
+    of state x [B, ..., 4] from the network output `out` at the evaluation record e, correction of x0 ('none' | 'clamp' |
+    'dynamic': dynamic thresholding at quantile `ratio`, floor `max_val`; a sample is one entry of dim 0) and -- with upd
+    (a dpm.program update) -- the solver update.  Samples past the kernel's register-resident size (PX_MAX_ROWS rows,
+    dynamic only), or fused=False, run the composed chain (thresh_chain + dpm_update_chain).  -> (m0, y or None)."""
+    _need_gpu(x, out)
+    ts = [t for t in (x, out, base, h1, h2) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape for t in ts)
+    kw = _px_common(x, out, correct, ratio, max_val)
+    if not fused or (correct == 'dynamic' and kw['rows_per_sample'] > PX_MAX_ROWS):
+        m0 = thresh_chain(x, out, e, target=target, correct=correct, ratio=ratio, max_val=max_val)
+        return m0, (None if upd is None else dpm_update_chain(upd, base, m0, h1, h2))
+    m0 = torch.empty_like(x)
+    y = None
+    if upd is not None:
+        y = torch.empty_like(x)
+        kw.update(mode=upd['mode'], base=_p(base), h1=_p(h1), h2=_p(h2), y=_p(y),
+                  **{k: float(upd[k]) for k in ('c0', 'c1', 'c2', 'c3', 'k0', 'k1', 'g', 'k2') if k in upd})
+    call('sdmi_dpm_step_px', _stream(), x=_p(x), out=_p(out), m0=_p(m0), target=_DPM_TARGET[target],
+         sigma=float(e['sigma']), alpha=float(e['alpha']), **kw)
+    return m0, y
+
+
+def unipc_step_px(x, out, rec, *, target='eps', correct='dynamic', ratio=0.995, max_val=1.0, base=None, h1=None,
+                  h2=None, h3=None, m0=None, xc=None, y=None, fused=True):
+    """One UniPC function evaluation's tail of an image-space model in one launch (sdmi.h: sdmi_unipc_step_px):
+    ops.unipc_step with the correction of dpm_step_px in the place of the code search.  -> (m0, xc or None, y or None)."""
+    _need_gpu(x, out)
+    corr, pred = rec['corr'], rec['pred']
+    ts = [t for t in (x, out, base, h1, h2, h3, m0, xc, y) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape for t in ts)
+    kw = _px_common(x, out, correct, ratio, max_val)
+    if not fused or (correct == 'dynamic' and kw['rows_per_sample'] > PX_MAX_ROWS):
+        mc = thresh_chain(x, out, rec['e'], target=target, correct=correct, ratio=ratio, max_val=max_val)
+        m0 = mc if m0 is None else m0.copy_(mc)
+        return (m0,) + unipc_update_chain(rec, base, m0, h1, h2, h3, xc=xc, y=y)
+    m0 = torch.empty_like(x) if m0 is None else m0
+    if corr is not None:
+        xc = torch.empty_like(x) if xc is None else xc
+        kw.update(corr_order=corr['order'], xc=_p(xc), **{k: float(corr[k]) for k in ('c0', 'c1', 'w1', 'w2', 'wn')})
+    else:
+        xc = None
+    if pred is not None:
+        y = torch.empty_like(x) if y is None else y
+        kw.update(pred_order=pred['order'], y=_p(y), p0=float(pred['c0']), p1=float(pred['c1']), q1=float(pred['q1']),
+                  q2=float(pred['q2']))
+    else:
+        y = None
+    call('sdmi_unipc_step_px', _stream(), x=_p(x), out=_p(out), m0=_p(m0), target=_DPM_TARGET[target],
+         sigma=float(rec['e']['sigma']), alpha=float(rec['e']['alpha']), base=_p(base), h1=_p(h1), h2=_p(h2), h3=_p(h3),
+         **kw)
+    return m0, xc, y
+
+
 def lincomb(c0=0., x0=None, c1=0., x1=None, c2=0., x2=None, x3=None, div=0., out=None):
     """out = ((c0*x0 + c1*x1) + c2*(x2 - x3)) / div  (fp32 tensors; see sdmi.h)."""
     ref = x0 if x0 is not None else (x1 if x1 is not None else x2)

@@ -370,12 +370,15 @@ def ddpm_buffers(prefix, timesteps):
 
 
 def ldm(prefix, dec_dict):
-    """`dm_decoder` of SADiffusion / SAViDiffusion (reference ldm.py:21-57)."""
+    """`dm_decoder` of SADiffusion / SAViDiffusion: LDM (reference ldm.py:21-57) or, for a dec_dict without `vae_dict`,
+    the image-space CondDDPM (cond_ddpm.py:21-53; sa_diffusion.py:141-148 chooses), whose state dict has no
+    `dm_decoder.vae.*`."""
     dd = dec_dict['diffusion_dict']
     out = ddpm_buffers(prefix, dd.get('timesteps', 1000))
     out += unet(f'{prefix}.model.diffusion_model', dec_dict['unet_dict'])
-    va = dec_dict['vae_dict']
-    out += vqvae(f'{prefix}.vae.vqvae', va['enc_dec_dict'], va['vq_dict'])
+    va = dec_dict.get('vae_dict')
+    if va:                 # without a VAE config the decoder is CondDDPM: the same UNet on the image itself
+        out += vqvae(f'{prefix}.vae.vqvae', va['enc_dec_dict'], va['vq_dict'])
     return out
 
 

@@ -40,14 +40,17 @@ VARIANTS = ('bh1', 'bh2')
 
 
 def check_options(order=3, variant='bh2', skip_type='time_uniform', steps=None, method='multistep',
-                  solver_type='dpmsolver', algorithm_type='dpmsolver++', correcting_x0_fn=None, guidance_scale=1.):
+                  solver_type='dpmsolver', algorithm_type='dpmsolver++', correcting_x0_fn=None, guidance_scale=1.,
+                  vq_denoised=True, dynamic_thresholding_ratio=0.995, thresholding_max_val=1.0):
     """ValueError naming the argument for everything this sampler does not build.  What dpm.check_options refuses
-    (taylor, the noise-prediction form, dynamic thresholding, guidance, orders outside 1..3, unknown grids) is refused
+    (taylor, the noise-prediction form, dynamic thresholding on a latent decoder, guidance, orders outside 1..3, unknown grids) is refused
     by it; on top of that only the multistep form and the variants bh1 / bh2 exist, and steps >= order."""
     if method != 'multistep':
         raise ValueError(f"method={method!r}: only multistep UniPC is built")
     dpm.check_options(method='multistep', order=order, skip_type=skip_type, solver_type=solver_type,
-                      algorithm_type=algorithm_type, correcting_x0_fn=correcting_x0_fn, guidance_scale=guidance_scale)
+                      algorithm_type=algorithm_type, correcting_x0_fn=correcting_x0_fn, guidance_scale=guidance_scale,
+                      vq_denoised=vq_denoised, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                      thresholding_max_val=thresholding_max_val)
     if variant not in VARIANTS:
         raise ValueError(f"variant={variant!r}: built are {VARIANTS} ('vary_coeff' is not)")
     if steps is not None and steps < order:
