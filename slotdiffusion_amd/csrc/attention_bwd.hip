@@ -469,8 +469,10 @@ extern "C" int sdmi_attention_bwd(const SdmiAttnBwdArgs* a, void* stream) {
   // chunked staging: any sequence length on either side (slot cross-attention under 28 x 28 queries
   // included: one wave walking the query chunks with MFMAs beats the thread-per-(key, channel) kernel
   // below by an order of magnitude there)
-  if (a->dtype == SDMI_BF16 && hd == 32)
+  if (a->dtype == SDMI_BF16 && hd == 32) {
+    SDMI_REQUIRE(a->Skv >= 1, "Skv must be positive");
     return launch_attn_bwd_mfma(*a, st);
+  }
   SDMI_REQUIRE(a->Skv >= 1 && a->Skv <= 400, "Skv must be in [1, 400] (fp32 / head_dim 48: K/V staged whole in LDS)");
   if (a->dtype == SDMI_BF16)
     return hd == 32 ? launch_attn_bwd<bf16_t, 32>(*a, st) : launch_attn_bwd<bf16_t, 48>(*a, st);
