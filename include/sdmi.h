@@ -167,6 +167,16 @@ typedef struct {
                        them later with sdmi_wgrad_fold_group (one launch for up to 16 layers) */
 } SdmiWgradArgs;
 int sdmi_wgrad(const SdmiWgradArgs* a, void* stream);
+/* Host-side query, no launch (pointers are not read): the kernel sdmi_wgrad dispatches for these arguments -- the
+ * launcher's own selection, so a caller that sizes `splits` for one of the direct kernels can check that it gets it. */
+enum {
+  SDMI_WGRAD_KERNEL_IGEMM = 0,       /* bf16 implicit GEMM (any tile / loader variant) */
+  SDMI_WGRAD_KERNEL_C64 = 1,         /* direct 3x3, 64 -> 64 channels */
+  SDMI_WGRAD_KERNEL_HALO = 2,        /* direct 3x3 on (64 output x 64 input channel) pairs */
+  SDMI_WGRAD_KERNEL_F32_T128 = 3,    /* exact fp32, 128 x 128 tiles */
+  SDMI_WGRAD_KERNEL_F32_T64 = 4      /* exact fp32, 64 x 64 tiles */
+};
+int sdmi_wgrad_kernel(const SdmiWgradArgs* a, void* stream);
 /* Fold the split partials of up to 16 earlier sdmi_wgrad(defer_fold = 1) launches into their dw / dbias
  * (+= when accumulate) in ONE launch.  `problems` (see SdmiWgradGroupArgs below) is a HOST array of the
  * same SdmiWgradArgs (dw, dbias, workspace, N, K, splits, accumulate are read); destinations must be

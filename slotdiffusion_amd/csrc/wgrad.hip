@@ -762,22 +762,57 @@ static bool wgrad_is1x1(const SdmiWgradArgs& a) {
          a.H == a.Ho && a.W == a.Wo;
 }
 
-int dispatch_wgrad_f32(const SdmiWgradArgs& a, hipStream_t st) {
+// Which kernel a problem takes is decided by the two select_* functions alone: the dispatchers below launch what they
+// answer and sdmi_wgrad_kernel reports it, so query and launch cannot disagree.
+int select_wgrad_f32(const SdmiWgradArgs& a) {
   // exact-fp32 MFMA runs at 1/16 of the bf16 rate (0.6 TFLOP/s per CU), so a launch with few workgroups is
   // COMPUTE bound on the handful of CUs it occupies: the Slot Attention / predictor layers (M = clips x slots
   // = 240 ... 448 rows, N, K <= 768) gave 4 - 36 workgroups of 128 x 128 and took 34 - 50 us each.  Below 96
   // workgroups the 64 x 64 tiles (four times the workgroups, a quarter of the work each) are used.
   const long long wg128 = (long long)((a.N + 127) / 128) * ((a.K + 127) / 128) * a.splits;
   const bool small = a.N <= 64 || a.K <= 64 || wg128 < 96;
+  return small ? SDMI_WGRAD_KERNEL_F32_T64 : SDMI_WGRAD_KERNEL_F32_T128;
+}
+
+int dispatch_wgrad_f32(const SdmiWgradArgs& a, hipStream_t st) {
   const bool is1x1 = wgrad_is1x1(a);
-  if (small)
+  if (select_wgrad_f32(a) == SDMI_WGRAD_KERNEL_F32_T64)
     return is1x1 ? launch_wgrad<float, 64, 64, true>(a, st)
                  : launch_wgrad<float, 64, 64, false>(a, st);
   return is1x1 ? launch_wgrad<float, 128, 128, true>(a, st)
                : launch_wgrad<float, 128, 128, false>(a, st);
 }
 
+int select_wgrad_bf16(const SdmiWgradArgs& a) {
+  // direct kernel for the 64 -> 64 channel 3x3 layers at full resolution (one workgroup per M-split slot)
+  if (a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && !a.ups && a.Cin == 64 &&
+      a.N == 64 && a.K == 576 && a.H == a.Ho && a.W == a.Wo && a.W % 64 == 0 && a.H % 4 == 0 && a.splits >= 2 &&
+      (long long)a.B * (a.H / 4) * (a.W / 64) >= a.splits && (long long)a.B * a.H * a.W * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
+    return SDMI_WGRAD_KERNEL_C64;
+  // ... and for every other 3x3 stride-1 layer on 16 / 32 / 64-column power-of-two images (pairs of 64 output x 64
+  // input channels; the caller sizes `splits` so that pairs x splits fills the chip: bwd.py).  The kernel always
+  // writes M-split partials for the fold behind it, so -- like the 64-channel kernel above -- it takes splits >= 2 only:
+  // splits == 1 means "written straight into dw" at the C ABI and goes to the implicit-GEMM kernel.
+  static int halo = -1;
+  if (halo < 0) {
+    const char* e = getenv("SDMI_WGRAD_HALO");
+    halo = e ? atoi(e) : 1;
+  }
+  const int logw = a.W == 16 ? 4 : (a.W == 32 ? 5 : (a.W == 64 ? 6 : 0));
+  const long long hw = (long long)a.H * a.W;
+  if (halo && logw && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && !a.ups && a.H == a.Ho &&
+      a.W == a.Wo && a.Cin % 64 == 0 && a.N % 64 == 0 && a.K == 9 * a.Cin && hw % 256 == 0 && (hw & (hw - 1)) == 0 &&
+      a.splits >= 2 && a.M / 256 >= a.splits && (a.N / 64) * (a.Cin / 64) * a.splits >= 128 &&
+      (long long)a.M * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
+    return SDMI_WGRAD_KERNEL_HALO;
+  return SDMI_WGRAD_KERNEL_IGEMM;
+}
+
 int dispatch_wgrad_bf16(const SdmiWgradArgs& a, hipStream_t st) {
+  const int which = select_wgrad_bf16(a);
+  if (which == SDMI_WGRAD_KERNEL_C64) return launch_wgrad3x3_c64(a, st);
+  if (which == SDMI_WGRAD_KERNEL_HALO)
+    return a.W == 16 ? launch_wgrad3x3_halo<4>(a, st) : (a.W == 32 ? launch_wgrad3x3_halo<5>(a, st) : launch_wgrad3x3_halo<6>(a, st));
   const bool is1x1 = wgrad_is1x1(a);
   const bool n64 = a.N <= 64, k64 = a.K <= 64;
   // "same" stride-1 convolution on a power-of-two image: the input pixel is linear in m
@@ -786,37 +821,23 @@ int dispatch_wgrad_bf16(const SdmiWgradArgs& a, hipStream_t st) {
   const long long mps = ((long long)a.M + a.splits - 1) / a.splits + 64;
   const long long ld = a.lda > a.ldy ? a.lda : a.ldy;
   const bool fits = (mps + (long long)(a.KH + 1) * a.W + 64) * ld * 2 < (1ll << 31);
-  // direct kernel for the 64 -> 64 channel 3x3 layers at full resolution (one workgroup per M-split slot)
-  {
-    if (a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && !a.ups && a.Cin == 64 &&
-        a.N == 64 && a.K == 576 && a.H == a.Ho && a.W == a.Wo && a.W % 64 == 0 && a.H % 4 == 0 && a.splits >= 2 &&
-        (long long)a.B * (a.H / 4) * (a.W / 64) >= a.splits && (long long)a.B * a.H * a.W * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
-      return launch_wgrad3x3_c64(a, st);
-  }
-  // ... and for every other 3x3 stride-1 layer on 16 / 32 / 64-column power-of-two images (pairs of 64 output x 64
-  // input channels; the caller sizes `splits` so that pairs x splits fills the chip: kern.py).  The kernel always
-  // writes M-split partials for the fold behind it, so -- like the 64-channel kernel above -- it takes splits >= 2 only:
-  // splits == 1 means "written straight into dw" at the C ABI and goes to the implicit-GEMM kernel below.
-  {
-    static int halo = -1;
-    if (halo < 0) {
-      const char* e = getenv("SDMI_WGRAD_HALO");
-      halo = e ? atoi(e) : 1;
-    }
-    const int logw = a.W == 16 ? 4 : (a.W == 32 ? 5 : (a.W == 64 ? 6 : 0));
-    const long long hw = (long long)a.H * a.W;
-    if (halo && logw && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && !a.ups && a.H == a.Ho &&
-        a.W == a.Wo && a.Cin % 64 == 0 && a.N % 64 == 0 && a.K == 9 * a.Cin && hw % 256 == 0 && (hw & (hw - 1)) == 0 &&
-        a.splits >= 2 && a.M / 256 >= a.splits && (a.N / 64) * (a.Cin / 64) * a.splits >= 128 &&
-        (long long)a.M * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
-      return logw == 4 ? launch_wgrad3x3_halo<4>(a, st) : (logw == 5 ? launch_wgrad3x3_halo<5>(a, st) : launch_wgrad3x3_halo<6>(a, st));
-  }
 #define WG_TR(TN, TK)                                                              \
   (is1x1 && fits ? launch_wgrad_tr<TN, TK, 1>(a, st)                               \
    : lin && fits ? launch_wgrad_tr<TN, TK, 2>(a, st) : launch_wgrad_tr<TN, TK, 0>(a, st))
   if (n64) return k64 ? WG_TR(64, 64) : WG_TR(64, 128);
   return k64 ? WG_TR(128, 64) : WG_TR(128, 128);
 #undef WG_TR
+}
+
+// the argument checks sdmi_wgrad and sdmi_wgrad_kernel share (everything but the pointers)
+const char* wgrad_geometry_error(const SdmiWgradArgs& a) {
+  if (a.dtype != SDMI_F32 && a.dtype != SDMI_BF16) return "bad dtype";
+  const int vec = a.dtype == SDMI_BF16 ? 8 : 4;
+  if (a.K != a.KH * a.KW * a.Cin) return "K != KH*KW*Cin";
+  if (a.Cin % vec != 0 || a.lda % vec != 0 || a.ldy % vec != 0) return "Cin/lda/ldy must be multiples of the 16-byte vector width";
+  if (a.M != a.B * a.Ho * a.Wo) return "M != B*Ho*Wo";
+  if (a.splits < 1) return "splits";
+  return nullptr;
 }
 
 }  // namespace
@@ -917,13 +938,8 @@ extern "C" int sdmi_wgrad_fold_group(const SdmiWgradGroupArgs* ga, void* stream)
 
 extern "C" int sdmi_wgrad(const SdmiWgradArgs* a, void* stream) {
   SDMI_REQUIRE(a && a->a && a->dy && a->dw && a->workspace, "null pointer");
-  SDMI_REQUIRE(a->dtype == SDMI_F32 || a->dtype == SDMI_BF16, "bad dtype");
-  const int vec = a->dtype == SDMI_BF16 ? 8 : 4;
-  SDMI_REQUIRE(a->K == a->KH * a->KW * a->Cin, "K != KH*KW*Cin");
-  SDMI_REQUIRE(a->Cin % vec == 0 && a->lda % vec == 0 && a->ldy % vec == 0,
-               "Cin/lda/ldy must be multiples of the 16-byte vector width");
-  SDMI_REQUIRE(a->M == a->B * a->Ho * a->Wo, "M != B*Ho*Wo");
-  SDMI_REQUIRE(a->splits >= 1, "splits");
+  const char* err = wgrad_geometry_error(*a);
+  SDMI_REQUIRE(!err, err);
   hipStream_t st = (hipStream_t)stream;
   int rc;
   rc = a->dtype == SDMI_BF16 ? dispatch_wgrad_bf16(*a, st) : dispatch_wgrad_f32(*a, st);
@@ -932,4 +948,11 @@ extern "C" int sdmi_wgrad(const SdmiWgradArgs* a, void* stream) {
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, *a);
   return sdmi_check_launch("wgrad reduce");
+}
+
+extern "C" int sdmi_wgrad_kernel(const SdmiWgradArgs* a, void*) {
+  SDMI_REQUIRE(a, "null pointer");
+  const char* err = wgrad_geometry_error(*a);
+  SDMI_REQUIRE(!err, err);
+  return a->dtype == SDMI_BF16 ? select_wgrad_bf16(*a) : select_wgrad_f32(*a);
 }

@@ -11,7 +11,6 @@ Both resolve weights through a WeightBank: fp32 operands are views of the master
 operands views of the bf16 shadow arena (same offsets); only channel-padded and non-adjacent
 fused operands are materialised.
 """
-import contextlib
 import ctypes
 import os
 from types import SimpleNamespace
@@ -19,7 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _lib, derived, ops, policy
+from . import _lib, bwd, derived, ops, policy
 from ._lib import call
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
@@ -306,31 +305,14 @@ class WeightBank:
         # then runs exactly the denoiser's backward (and stops at the slots), so that its gradient
         # range can be all-reduced while the slot encoder's backward is still running
         self.anchor_dec = torch.zeros(1, device=model.arena().device, requires_grad=True)
-        # weight-gradient GEMMs are off the backward critical path (nothing downstream reads them
-        # before the optimiser): they run on a second HIP stream, concurrently with the dgrad
-        # chain, and are joined when the autograd pass ends.  Their operands are kept alive until
-        # the join (HBM is plentiful), so no allocator stream bookkeeping is needed.
-        self.overlap_wgrad = bool(policy.flag('WGRAD_STREAM'))
-        self.n_side = 4
-        self._sides = []
-        self._pending, self._side_of = [], {}
-        self._join_queued = False
-        # grouped weight gradients (sdmi_wgrad_group): the fused SpatialTransformer backward queues a block's problems
-        # and launches them together (StBlockFn.backward_fused)
-        self._wq, self._wq_keep = [], []
+        # weight-gradient launches and the ordering of everything that writes the gradient arena (bwd.GradSchedule);
+        # its side streams on / off is `overlap_wgrad`
+        self.sched = bwd.GradSchedule(bool(policy.flag('WGRAD_STREAM')))
         self.defer_colsum = bool(policy.flag('DEFER_COLSUM'))
-        # data gradient + weight gradient of a layer in ONE launch on the main stream (sdmi_bwd_pair):
-        # no side-stream fork / join per layer, the M-split partials of a layer are folded by extra
-        # workgroups of the NEXT layer's launch (`_pfold`: the pending fold), the last one at the join
+        # data gradient + weight gradient of a layer in ONE launch on the main stream (sdmi_bwd_pair) where
+        # bwd.plan_layer finds the layer fit for it
         self.pair_bwd = bool(policy.flag('BWD_PAIR'))
-        # geometry of a pair launch (round-3 sweeps, profiles/r03_pair_sweep.txt): resident workgroups (2 per CU), of
-        # which walk dX tiles, 64-row steps per weight-gradient workgroup, 64 x 64 dW tiles below this many of them
-        self.pair_slots, self.pair_dgrad, self.pair_min_steps, self.pair_wt64 = 512, 256, 8, 96
-        self._pfold = None
-        # gradient destinations a side-stream launch of this backward wrote: a main-stream writer of the same
-        # destination (pair launch, pending fold) waits for that stream first
-        self._side_dst = {}
-        self._cq, self._wq_flushes, self._fz = [], 0, None
+        self._fz = None
         # derived operands re-made once per optimiser step, each family by ONE launch over its device-side descriptor
         # table (derived.StepTable): dgrad operands (wd / wd_sub, one table per dtype), e4m3fn operands with device-side
         # scales (w8_dev: descriptor i = slot i of _q_amax / _q_inv) and the unit streams of the fused
@@ -348,175 +330,17 @@ class WeightBank:
         n = names if isinstance(names, str) else names[0]
         return self.anchor_dec if n.startswith('dm_decoder') else self.anchor
 
-    def side_index(self, key):
-        """Side stream of a parameter (by name): a parameter used several times per step (Slot
-        Attention iterations, the per-frame predictor) accumulates its gradient in stream order on
-        ONE stream; different parameters are spread round-robin."""
-        i = self._side_of.get(key)
-        if i is None:
-            i = self._side_of[key] = len(self._side_of) % self.n_side
-        return i
+    overlap_wgrad = property(lambda self: self.sched.overlap, lambda self, on: setattr(self.sched, 'overlap', bool(on)))
 
-    def side_stream(self, key=None):
-        if not self.overlap_wgrad:
-            return None
-        # a few streams: most weight-gradient launches are small (<= 128 workgroups + their
-        # reduction) and several of them fit the chip next to the dgrad chain
-        if not self._sides:
-            self._sides = [torch.cuda.Stream() for _ in range(self.n_side)]
-        return self._sides[self.side_index(key)]
-
-    def ensure_join(self):
-        if not self._join_queued:
-            self._join_queued = True
-            torch.autograd.Variable._execution_engine.queue_callback(self.join)
-
-    def defer(self, *tensors):
-        self._pending.append(tensors)
-        self.ensure_join()
-
-    # ---- grouped weight gradients (sdmi_wgrad_group) ----------------------------------------------
-    WQ_TARGET = 512.0          # workgroups of a grouped launch, shared by the problems in proportion to their work
-
-    def flush_wgrad(self):
-        """Launch the queued bf16 1x1 / linear weight-gradient problems (`_wq`: (sdmi_wgrad fields, 128 x 128 tiles, 64-row
-        steps)) as ONE sdmi_wgrad_group call on a side stream; M-splits chosen here.  -> the stream it ran on."""
-        if not self._wq:
-            return None
-        q, keep = self._wq, self._wq_keep
-        self._wq, self._wq_keep = [], []
-        # M-splits: ~512 workgroups over the group, shared in proportion to each problem's work
-        # (tiles x 64-row steps), every split keeping >= 8 steps
-        work = [t * st for _, t, st in q]
-        total = float(sum(work))
-        splits = []
-        for (kw, t, st), w in zip(q, work):
-            want = max(1, int(round(self.WQ_TARGET * w / total / t)))
-            splits.append(max(1, min(want, st // 8, 64)))
-        ws_len = sum(sp * (kw['N'] * kw['K'] + kw['N']) for (kw, _, _), sp in zip(q, splits) if sp > 1)
-        dev = keep[0].device
-        ws = torch.empty((max(ws_len, 1),), dtype=torch.float32, device=dev)
-        off, rows = 0, []
-        for (kw, _, _), sp in zip(q, splits):
-            rows.append(dict(kw, splits=sp))
-            if sp > 1:
-                rows[-1]['workspace'] = ws.data_ptr() + 4 * off
-                off += sp * (kw['N'] * kw['K'] + kw['N'])
-        arr = _lib.struct_array('SdmiWgradArgs', rows)
-        flops = sum(2.0 * kw['M'] * kw['N'] * kw['K'] for kw, _, _ in q)
-        self._wq_flushes += 1
-        side = self.side_stream(f'wgrad-group-{self._wq_flushes % self.n_side}')
-        if side is not None:
-            ev = torch.cuda.Event()
-            ev.record()
-            side.wait_event(ev)
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            call('sdmi_wgrad_group', _st(), problems=ctypes.addressof(arr), n=len(q),
-                 _meta=dict(flops=flops))
-        self._pending.append(tuple(keep) + (ws,))
-        return side
-
-    # ---- deferred dgamma / dbeta folds of the normalisation backward passes ---------------------
     def queue_colsum(self, partial, nblk, C, out0, out1):
-        self._cq.append((partial, nblk, C, out0, out1))
-        self.ensure_join()
+        self.sched.queue_colsum(partial, nblk, C, out0, out1)
 
-    def flush_colsum(self):
-        q, self._cq = self._cq, []
-        # a parameter used several times per step (Slot Attention iterations, per-frame modules)
-        # has several items with the same destination: they go to successive launches (the
-        # workgroups of one launch read-modify-write their destinations concurrently)
-        chunks = []
-        for it in q:
-            for ch in chunks:
-                if len(ch[0]) < 64 and _p(it[3]) not in ch[1]:
-                    break
-            else:
-                ch = ([], set())
-                chunks.append(ch)
-            ch[0].append(it)
-            ch[1].add(_p(it[3]))
-        for chunk, _ in chunks:
-            arr = _lib.struct_array('SdmiColsumItem', (dict(partial=_p(partial), out0=_p(o0), out1=_p(o1), nblk=nblk, C=C)
-                                                       for partial, nblk, C, o0, o1 in chunk))
-            call('sdmi_colsum_group', _st(), items=ctypes.addressof(arr), n=len(chunk))
-        # (the partial buffers die with q: the launches above are ordered before their reuse)
-
-    # ---- fused data + weight gradient launches --------------------------------------------------
-    def flush_pending_fold(self, dst_ptrs=None):
-        """Fold the pending M-split partials now (own launch).  dst_ptrs given: only when the pending
-        fold targets one of these gradient buffers (a parameter used again before its fold ran)."""
-        pf = self._pfold
-        if pf is None:
-            return
-        if dst_ptrs is not None and pf[0]['dw'] not in dst_ptrs and (not pf[0]['dbias'] or pf[0]['dbias'] not in dst_ptrs):
-            return
-        self._pfold = None
-        self._after_side_writers(pf[0]['dw'], pf[0]['dbias'])
-        arr = _lib.struct_array('SdmiWgradArgs', [pf[0]])
-        call('sdmi_wgrad_fold_group', _st(), problems=ctypes.addressof(arr), n=1)
-
-    def _after_side_writers(self, *ptrs):
-        """Main stream waits for side streams that have launches into any of these destinations in flight."""
-        for p_ in ptrs:
-            side = self._side_dst.pop(p_, None) if p_ else None
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
-
-    def pair_launch(self, dkw, wkw, keep):
-        """One sdmi_bwd_pair launch: dkw / wkw are the sdmi_igemm / sdmi_wgrad fields of the layer's data
-        and weight gradient; M-split chosen here (the weight-gradient workgroups take what the data
-        gradient leaves of `pair_slots` resident workgroups, >= pair_min_steps 64-row steps each)."""
-        M, N, K = wkw['M'], wkw['N'], wkw['K']
-        t128 = ((dkw['M'] + 127) // 128) * ((dkw['N'] + 127) // 128)
-        shallow = dkw['KH'] == 1 and dkw['KW'] == 1 and dkw['K'] * 2 <= 512
-        big = t128 >= 192 and not shallow
-        tiles_d = t128 if big else ((dkw['M'] + 63) // 64) * ((dkw['N'] + 63) // 64)
-        steps = (M + 63) // 64
-
-        def plan(wt, slots, min_steps):
-            tn = (N + wt - 1) // wt
-            tiles_w = tn * ((K + wt - 1) // wt) + (tn if wkw['dbias'] else 0)
-            n_d = min(tiles_d, self.pair_dgrad)
-            return tiles_w, n_d, max(1, min((slots - n_d) // tiles_w, steps // min_steps, 256))
-        wt = 128
-        tiles_w, n_d, splits = plan(128, self.pair_slots, self.pair_min_steps)
-        if not big and self.pair_wt64 and tiles_w * splits < self.pair_wt64:
-            # a small layer: 64 x 64 weight-gradient tiles -- four times the workgroups, three per CU
-            wt = 64
-            tiles_w, n_d, splits = plan(64, self.pair_slots * 3 // 2, max(2, self.pair_min_steps // 2))
-        self.flush_pending_fold((wkw['dw'], wkw['dbias']))      # this parameter again: fold first
-        self._after_side_writers(wkw['dw'], wkw['dbias'])
-        ws = None
-        if splits > 1:
-            ws = torch.empty((splits * (N * K + N),), dtype=torch.float32, device=keep[0].device)
-        pf, self._pfold = self._pfold, None
-        if pf is not None:
-            self._after_side_writers(pf[0]['dw'], pf[0]['dbias'])
-        d = _lib.struct_array('SdmiGemmArgs', [dkw])
-        w = _lib.struct_array('SdmiWgradArgs', [dict(wkw, splits=splits, workspace=_p(ws), defer_fold=1)])
-        f = _lib.struct_array('SdmiWgradArgs', [pf[0]]) if pf is not None else None
-        call('sdmi_bwd_pair', _st(), dgrad=ctypes.addressof(d), wgrad=ctypes.addressof(w),
-             fold=(ctypes.addressof(f) if pf is not None else 0), dgrad_cap=((n_d + 7) // 8 * 8), wgrad_tile=wt,
-             _meta=dict(flops=2.0 * dkw['M'] * dkw['N'] * dkw['K'] + 2.0 * M * N * K,
-                        flops_dgrad=2.0 * dkw['M'] * dkw['N'] * dkw['K'],
-                        bytes=float(2 * (dkw['M'] * dkw['K'] // (dkw['KH'] * dkw['KW']) + dkw['N'] * dkw['K']
-                                         + dkw['M'] * dkw['N'] * (2 if dkw.get('residual', 0) else 1)
-                                         + M * wkw['Cin']) + 4 * N * K)))
-        if splits > 1:            # folded by the next pair launch (or at the join)
-            self._pfold = (dict(dw=wkw['dw'], dbias=wkw['dbias'], workspace=_p(ws), N=N, K=K, splits=splits,
-                                accumulate=wkw['accumulate']), ws)
-            self.ensure_join()
+    def join_by_hand(self):
+        """Backward kernels called outside an autograd pass: the caller calls join() itself."""
+        self.sched.join_by_hand()
 
     def join(self):
-        self.flush_pending_fold()
-        self.flush_wgrad()
-        self.flush_colsum()
-        for side in self._sides:
-            torch.cuda.current_stream().wait_stream(side)
-        self._pending.clear()
-        self._side_dst.clear()
-        self._join_queued = False
+        self.sched.join()
 
     def invalidate(self):
         """The master weights changed (optimiser step / checkpoint load): derived operands of
@@ -1448,179 +1272,88 @@ class GemmFn(torch.autograd.Function):
 
     @staticmethod
     def core(wb, x, dy, wnames, bnames, geom, need_dx, dalias=None):
-        """Weight / bias gradient (queued or launched) and data gradient of one conv / linear.
-        -> (dx or None, dy in the compute dtype, (N, ldy, B, Ho, Wo, dt))."""
-        kh, kw, stride, pad, ups = geom
-        is_conv = x.dim() == 4 and (kh, kw) != (0, 0)
-        if not is_conv:
-            kh = kw = 1
-            stride, pad, ups = 1, (0, 0, 0, 0), False
+        """Weight / bias gradient and data gradient of one conv / linear: build the problem, plan (bwd.plan_layer),
+        execute the plan.  -> (dx or None, dy in the compute dtype, (N, ldy, B, Ho, Wo, dt))."""
         dt = x.dtype
         vec = ops.vec_of(dt)
-        w = wb.w(wnames, dt)
-        N = w.shape[0]
+        N = wb.w(wnames, dt).shape[0]
         dy = dy.contiguous()
         # bring dY to the compute dtype with a vector-multiple row pitch
         if dy.dtype != dt or dy.shape[-1] % vec:
             npad = (N + vec - 1) // vec * vec
             dy = ops.cast2d(dy, dt, cols=N, ldd=npad)
-        ldy = dy.shape[-1]
-        Cin = x.shape[-1]
-        if is_conv:
-            B, H, W_, _ = x.shape
-            Ho, Wo = dy.shape[1], dy.shape[2]
-        else:
-            B, H, W_, Ho, Wo = x.numel() // Cin, 1, 1, 1, 1
-        M = B * Ho * Wo
-        K = kh * kw * Cin
-        # ---- weight / bias gradients straight into the gradient arena
+        P = bwd.LayerProblem.of(x, dy, geom, dt, N)
+        info = (N, P.ldy, P.B, P.Ho, P.Wo, dt)
+        # weight / bias gradients go straight into the gradient arena where it has the kernel's [N][K] layout
         names = (wnames,) if isinstance(wnames, str) else tuple(wnames)
         dst = _grads_of(wb, names)
-        k_true = wb.t[names[0]].numel() // wb.t[names[0]].shape[0]
-        direct = dst is not None and k_true == K
-        tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        # M is split so that ~0.75 workgroups per CU exist (the launches share the chip with the
-        # dgrad chain and three more weight-gradient streams; sweep 128 ... 768 on one box: 192-256
-        # best, 512 is +0.7 ... +1.8 ms per step) while each still walks >= 8 m-steps
-        # (64 rows per step in the bf16 kernel, 32 in the fp32 one); short contractions take one
-        # launch straight into the gradient arena
-        mt = 64 if dt == torch.bfloat16 else 32
-        splits = max(1, min((192 + tiles - 1) // tiles, M // (8 * mt), 512))
-        if M <= 16 * mt:
-            splits = 1
-        if (dt == torch.bfloat16 and is_conv and kh == 3 and kw == 3 and stride == 1 and not ups and Cin == 64
-                and N == 64 and tuple(pad) == (1, 1, 1, 1) and W_ % 64 == 0 and H % 4 == 0
-                and B * (H // 4) * (W_ // 64) >= 2 * _n_cus(x.device)):
-            # the direct 3x3 kernel (wgrad.hip: wgrad3x3_c64_kernel): one persistent workgroup per CU and slot
-            splits = _n_cus(x.device)
-        elif (dt == torch.bfloat16 and is_conv and kh == 3 and kw == 3 and stride == 1 and not ups and _WGRAD_HALO
-                and tuple(pad) == (1, 1, 1, 1) and W_ in (16, 32, 64) and Cin % 64 == 0 and N % 64 == 0 and Ho == H and Wo == W_
-                and (H * W_) % 256 == 0 and ((H * W_) & (H * W_ - 1)) == 0):
-            # the direct 3x3 kernel on (64 output x 64 input channel) pairs (wgrad.hip: wgrad3x3_halo_kernel): one
-            # persistent workgroup per CU -- slots x pairs fills the chip
-            pairs = (N // 64) * (Cin // 64)
-            halo_splits = min(_n_cus(x.device) // pairs, M // 256)
-            if halo_splits >= 2 and pairs * halo_splits >= 128:        # (the kernel writes partials: never one split)
-                splits = halo_splits
         bdst = _grads_of(wb, bnames) if bnames is not None else None
-        lda = Cin if is_conv else x.stride(-2)
-        # ---- data + weight gradient in ONE launch (sdmi_bwd_pair) when both are of the same loader
-        # class: 1x1 / linear, or a stride-1 same-size convolution
-        same = is_conv and stride == 1 and not ups and Ho == H and Wo == W_
-        one = kh == 1 and kw == 1 and stride == 1 and not ups and pad[0] == 0 and pad[2] == 0
-        kd = kh * kw * ldy                                   # contraction depth of the data gradient
-        bk = 64 if kd * 2 >= 512 else 32
-        pair = (wb.pair_bwd and need_dx and dt == torch.bfloat16 and direct and N > 64 and K > 64 and Cin > 64
-                and (bnames is None or bdst is not None) and Cin % 8 == 0 and ldy % 8 == 0
-                and (one or (same and kh * kw <= 32 and ldy % bk == 0
-                             and pad[0] == pad[1] == (kh - 1) // 2 and pad[2] == pad[3] == (kw - 1) // 2))
-                and (dalias is None or dalias.shape[-1] == Cin)
-                and (M + (kh + 1) * W_ + 128) * max(lda, ldy, Cin) * 2 < (1 << 31) and N * kd * 2 < (1 << 31))
-        if pair:
-            wd = wb.wd(wnames, dt, kh, kw, Cin)
-            dx = torch.empty(x.shape if not is_conv else (B, H, W_, Cin), dtype=dt, device=x.device)
-            wb.pair_launch(
-                dict(a=_p(dy), w=_p(wd), out=_p(dx), dtype=_DT[dt], out_dtype=_DT[dt], M=M, N=Cin, K=kd,
-                     lda=ldy, ldw=kd, ldc=Cin, B=B, H=Ho, W=Wo, Cin=ldy, Ho=H, Wo=W_, KH=kh, KW=kw, stride=1,
-                     pad_t=kh - 1 - pad[0], pad_l=kw - 1 - pad[2], ups=0, act=0, alpha=1.0, split_k=1, batch=1,
-                     residual=_p(dalias), ldr=Cin),
-                dict(a=_p(x), dy=_p(dy), dw=_p(dst), dbias=_p(bdst), dtype=_DT[dt], M=M, N=N, K=K, lda=lda,
-                     ldy=ldy, B=B, H=H, W=W_, Cin=Cin, Ho=Ho, Wo=Wo, KH=kh, KW=kw, stride=stride,
-                     pad_t=pad[0], pad_l=pad[2], ups=0, accumulate=1),
-                (x, dy, dx))
-            return dx, dy, (N, ldy, B, Ho, Wo, dt)
-        wb.flush_pending_fold((_p(dst), _p(bdst)))     # (a pending fold into this parameter goes first)
-        side = wb.side_stream(names[0])
-        if side is not None:
-            ev = torch.cuda.Event()
-            ev.record()
-            side.wait_event(ev)          # dy is ready
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            GemmFn._wgrad(wb, x, dy, dt, names, bnames, dst, direct, splits, M, N, K, Cin, ldy, B,
-                          H, W_, Ho, Wo, kh, kw, stride, pad, ups, is_conv)
-        if side is not None:
-            wb.defer(x, dy)
-            wb._side_dst[_p(dst)] = side
-            if bdst is not None:
-                wb._side_dst[_p(bdst)] = side
+        direct = dst is not None and wb.t[names[0]].numel() // wb.t[names[0]].shape[0] == P.K
+        plan = bwd.plan_layer(P, need_dx=need_dx, direct=direct, has_bias=bnames is not None, bias_dst=bdst is not None,
+                              dalias_cols=(dalias.shape[-1] if dalias is not None else None), n_cus=_n_cus(x.device),
+                              pair_bwd=wb.pair_bwd, wgrad_halo=_WGRAD_HALO)
+        if plan.path == 'pair':
+            wd = wb.wd(wnames, dt, P.kh, P.kw, P.Cin)
+            dx = torch.empty(x.shape if not P.is_conv else (P.B, P.H, P.W, P.Cin), dtype=dt, device=x.device)
+            wb.sched.launch_pair(
+                P, plan.pair,
+                dict(P.dgrad_fields(), a=_p(dy), w=_p(wd), out=_p(dx), split_k=1, residual=_p(dalias)),
+                dict(P.wgrad_fields(), a=_p(x), dy=_p(dy), dw=_p(dst), dbias=_p(bdst), accumulate=1), x.device)
+            return dx, dy, info
+        wb.sched.side_wgrad(names[0], (_p(dst), _p(bdst)),
+                            lambda: GemmFn._wgrad(wb, x, dy, P, plan, names, bnames, dst, direct), (x, dy))
         # ---- data gradient: the forward kernel on the flipped operand
         dx = None
         if need_dx:
-            wd = wb.wd(wnames, dt, kh, kw, Cin)
-            if is_conv and stride > 1 and not ups:
+            wd = wb.wd(wnames, dt, P.kh, P.kw, P.Cin)
+            if P.is_conv and P.stride > 1 and not P.ups:
                 dx, dalias = GemmFn._dgrad_strided(
-                    dy, wd, B, H, W_, Ho, Wo, Cin, ldy, kh, kw, stride, pad, dt, dalias,
-                    sub_of=lambda a0, b0: wb.wd_sub(wnames, dt, kh, kw, Cin, a0, b0, stride))
-            elif is_conv:
-                Hs, Ws = (2 * H, 2 * W_) if ups else (H, W_)
-                out = torch.empty((B, Hs, Ws, Cin), dtype=dt, device=x.device)
-                ws = None if stride > 1 else ops.splitk_workspace(B * Hs * Ws, Cin, kh * kw * ldy,
-                                                                  dy.element_size(), x.device)
-                call('sdmi_igemm', _st(), a=_p(dy), w=_p(wd), out=_p(out), dtype=_DT[dt], workspace=_p(ws),
-                     out_dtype=_DT[dt], M=B * Hs * Ws, N=Cin, K=kh * kw * ldy, lda=ldy,
-                     ldw=kh * kw * ldy, ldc=Cin, B=B, H=Ho, W=Wo, Cin=ldy, Ho=Hs, Wo=Ws, KH=kh,
-                     KW=kw, stride=1, pad_t=kh - 1 - pad[0], pad_l=kw - 1 - pad[2], ups=0, act=0,
-                     alpha=1.0, split_k=(0 if ws is not None else 1), batch=1,
-                     zins=(stride if stride > 1 else 0), residual=(_p(dalias) if (dalias is not None and not ups) else 0), ldr=Cin)
-                if dalias is not None and not ups:
+                    dy, wd, P.B, P.H, P.W, P.Ho, P.Wo, P.Cin, P.ldy, P.kh, P.kw, P.stride, P.pad, dt, dalias,
+                    sub_of=lambda a0, b0: wb.wd_sub(wnames, dt, P.kh, P.kw, P.Cin, a0, b0, P.stride))
+            elif P.is_conv:
+                f = P.dgrad_fields()
+                out = torch.empty((P.B, f['Ho'], f['Wo'], P.Cin), dtype=dt, device=x.device)
+                ws = None if P.stride > 1 else ops.splitk_workspace(f['M'], P.Cin, f['K'], dy.element_size(), x.device)
+                fuse = dalias is not None and not P.ups
+                call('sdmi_igemm', _st(), a=_p(dy), w=_p(wd), out=_p(out), workspace=_p(ws),
+                     split_k=(0 if ws is not None else 1), residual=(_p(dalias) if fuse else 0), **f)
+                if fuse:
                     dalias = None
-                if ups:
+                if P.ups:
                     dx = torch.empty_like(x)
-                    call('sdmi_pool2x2_sum', _st(), x=_p(out), y=_p(dx), dtype=_DT[dt], B=B, H=H,
-                         W=W_, C=Cin)
+                    call('sdmi_pool2x2_sum', _st(), x=_p(out), y=_p(dx), dtype=_DT[dt], B=P.B, H=P.H, W=P.W, C=P.Cin)
                 else:
                     dx = out
             else:
-                dx = ops.linear(dy.view(-1, ldy), wd,
-                                residual=(dalias.view(-1, Cin) if dalias is not None else None)).view(x.shape)
+                dx = ops.linear(dy.view(-1, P.ldy), wd,
+                                residual=(dalias.view(-1, P.Cin) if dalias is not None else None)).view(x.shape)
                 dalias = None
             if dalias is not None:          # (no epilogue to fold it into: nearest-x2 / partial parity cover)
                 call('sdmi_add', _st(), x=_p(dx), z=_p(dalias), y=_p(dx), dtype=_DT[dt], n=dx.numel())
         elif dalias is not None:
             dx = dalias
-        return dx, dy, (N, ldy, B, Ho, Wo, dt)
+        return dx, dy, info
 
     @staticmethod
     def _dgrad_strided(dy, wd, B, H, W_, Ho, Wo, Cin, ldy, kh, kw, s, pad, dt, extra=None, sub_of=None):
-        """Data gradient of a stride-s convolution as s*s plain stride-1 convolutions over dy, one
-        per input-pixel parity (py, px): only the filter taps kh = (py + pad_t) mod s (+ s, ...)
-        reach that parity, so each launch uses its sub-filter (a strided slice of the flipped
-        operand) and writes its pixels interleaved into dx (igemm's sub-sampled output placement).
-        No multiply-adds on inserted zeros: 1/s^2 of the work of the zero-insertion form."""
+        """Data gradient of a stride-s convolution by input-pixel parity (bwd.LayerProblem.parity_dgrads)."""
+        full, subs = bwd.LayerProblem.conv(B, H, W_, Ho, Wo, Cin, ldy, ldy, kh, kw, s, pad, dt).parity_dgrads()
         w4 = wd.view(Cin, kh, kw, ldy)
-        full = all(len(range((p + pd) % s, k, s)) > 0
-                   for k, pd in ((kh, pad[0]), (kw, pad[2])) for p in range(s))
         dx = torch.empty((B, H, W_, Cin), dtype=dt, device=dy.device)
         if not full:
             ops.zero_(dx)
         # `extra` (gradient of x's other consumer) rides in the epilogue when every pixel is written
         fuse = extra is not None and full
-        for py in range(s):
-            ay = (py + pad[0]) % s
-            nky = len(range(ay, kh, s))
-            hs = len(range(py, H, s))
-            for px in range(s):
-                ax = (px + pad[2]) % s
-                nkx = len(range(ax, kw, s))
-                ws_ = len(range(px, W_, s))
-                if nky == 0 or nkx == 0 or hs == 0 or ws_ == 0:
-                    continue
-                sub = sub_of((kh - 1 - ay) % s, (kw - 1 - ax) % s) if sub_of is not None else \
-                    w4[:, (kh - 1 - ay) % s::s, (kw - 1 - ax) % s::s, :].contiguous()
-                K = nky * nkx * ldy
-                call('sdmi_igemm', _st(), a=_p(dy), w=_p(sub), out=_p(dx), dtype=_DT[dt],
-                     out_dtype=_DT[dt], M=B * hs * ws_, N=Cin, K=K, lda=ldy, ldw=K, ldc=Cin, B=B,
-                     H=Ho, W=Wo, Cin=ldy, Ho=hs, Wo=ws_, KH=nky, KW=nkx, stride=1,
-                     pad_t=(nky - 1) - (py + pad[0] - ay) // s, pad_l=(nkx - 1) - (px + pad[2] - ax) // s,
-                     ups=0, act=0, alpha=1.0, split_k=1, batch=1, oH=H, oW=W_, osy=s, osx=s, ooy=py,
-                     oox=px, residual=(_p(extra) if fuse else 0), ldr=Cin)
+        for a0, b0, f in subs:
+            sub = sub_of(a0, b0) if sub_of is not None else w4[:, a0::s, b0::s, :].contiguous()
+            call('sdmi_igemm', _st(), a=_p(dy), w=_p(sub), out=_p(dx), split_k=1, residual=(_p(extra) if fuse else 0), **f)
         return dx, (None if fuse else extra)
 
     @staticmethod
-    def _wgrad(wb, x, dy, dt, names, bnames, dst, direct, splits, M, N, K, Cin, ldy, B, H, W_, Ho,
-               Wo, kh, kw, stride, pad, ups, is_conv):
-        """Weight / bias gradient launches (on whatever stream is current)."""
-        ws = torch.empty((splits * (N * K + N),), dtype=torch.float32, device=x.device)
+    def _wgrad(wb, x, dy, P, plan, names, bnames, dst, direct):
+        """The stand-alone weight / bias gradient launches of problem P (on whatever stream is current)."""
+        N, K, Cin = P.N, P.K, P.Cin
+        ws = torch.empty((plan.splits * (N * K + N),), dtype=torch.float32, device=x.device)
         # (temporaries of non-direct destinations are overwritten by the kernel, then added to the arena)
         acc = 1 if direct else 0
         dwbuf = dst if direct else torch.empty((N, K), dtype=torch.float32, device=x.device)
@@ -1634,17 +1367,14 @@ class GemmFn(torch.autograd.Function):
                 btmp = torch.empty((N,), dtype=torch.float32, device=x.device)
                 if acc:
                     ops.zero_(btmp)
-        call('sdmi_wgrad', _st(), a=_p(x), dy=_p(dy), dw=_p(dwbuf), dbias=_p(btmp),
-             workspace=_p(ws), dtype=_DT[dt], M=M, N=N, K=K,
-             lda=(Cin if is_conv else x.stride(-2)), ldy=ldy, B=B, H=H, W=W_,
-             Cin=Cin, Ho=Ho, Wo=Wo, KH=kh, KW=kw, stride=stride, pad_t=pad[0], pad_l=pad[2],
-             ups=int(ups), splits=splits, accumulate=acc)
+        call('sdmi_wgrad', _st(), a=_p(x), dy=_p(dy), dw=_p(dwbuf), dbias=_p(btmp), workspace=_p(ws), splits=plan.splits,
+             accumulate=acc, **P.wgrad_fields())
         # non-direct destinations (channel-padded Cin, non-adjacent fused parameters) ACCUMULATE like
         # the direct path does: a parameter used several times per step (per-frame modules,
         # gradient accumulation over micro-batches) keeps every contribution
         if not direct:
             g = wb.model.grad_arena()
-            taps = kh * kw
+            taps = P.kh * P.kw
             o, segs, keep = 0, [], []
             for nme in names:
                 off, cnt = wb.model._offsets[nme]
@@ -2043,28 +1773,16 @@ class StBlockFn(torch.autograd.Function):
             if not _ST_WGRAD_GROUP or dst is None or (bn is not None and bdst is None):
                 GemmFn.core(wb, a, dy, wn, bn, lin, False)
                 return
-            M, K, N = a.numel() // a.shape[-1], a.shape[-1], dy.shape[-1]
-            kw = dict(a=_p(a), dy=_p(dy), dw=_p(dst), dbias=_p(bdst), dtype=_lib.BF16, M=M, N=N, K=K, lda=K, ldy=N, B=M,
-                      H=1, W=1, Cin=K, Ho=1, Wo=1, KH=1, KW=1, stride=1, pad_t=0, pad_l=0, ups=0, accumulate=1)
-            tn = (N + 127) // 128
-            grp.append((kw, tn * ((K + 127) // 128) + (tn if bn is not None else 0), (M + 63) // 64, a, dy))
+            P = bwd.LayerProblem.of(a, dy, lin, torch.bfloat16, dy.shape[-1])
+            grp.append((P, bn is not None, a, dy,
+                        dict(P.wgrad_fields(), a=_p(a), dy=_p(dy), dw=_p(dst), dbias=_p(bdst), accumulate=1)))
 
         def flush_group():
             if not grp:
                 return
-            wb.flush_wgrad()                       # (nothing of another layer rides in this launch)
-            for kw, tiles, steps, a, dy in grp:
-                wb.flush_pending_fold((kw['dw'], kw['dbias']))
-                wb._after_side_writers(kw['dw'], kw['dbias'])
-                wb._wq.append((kw, tiles, steps))
-                wb._wq_keep.extend((a, dy))
-            side = wb.flush_wgrad()
-            for kw, *_ in grp:
-                for d in (kw['dw'], kw['dbias']):
-                    if d and side is not None:
-                        wb._side_dst[d] = side
+            wb.sched.launch_group([g[4] for g in grp], bwd.plan_group([g[:2] for g in grp]),
+                                  [t_ for g in grp for t_ in g[2:4]], dev)
             del grp[:]
-            wb.ensure_join()
         F_ = lambda k: _p(wb.f(k))
         geo = dict(B=B, S=S, C=C, rows=rows)
         rf = 2.0 * B * S * C * C
@@ -2577,29 +2295,22 @@ class DropoutFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------
 # plain-SA decoder pieces (img_based/models/slot_attention.py:343-364)
 # ------------------------------------------------------------------------------------------
-def _deconv_geom(x, w, k, stride, pad):
-    B, H, W_, Cin = x.shape
-    Cout = w.shape[1] // (k * k)
-    Ho = (H - 1) * stride - 2 * pad + k + (stride - 1)
-    Wo = (W_ - 1) * stride - 2 * pad + k + (stride - 1)
-    return B, H, W_, Cin, Cout, Ho, Wo
+def _deconv_problem(wb, x, wname, k, stride, pad):
+    """The parameter [Cin, Cout, k, k] lies in the arena as [Cin][k][k][Cout] = the weight of the stride-`stride`
+    convolution this layer is the data gradient of: that convolution's backward problem (bwd.LayerProblem.transposed)."""
+    Cout = wb.w(wname, x.dtype).shape[1] // (k * k)
+    return bwd.LayerProblem.transposed(x, Cout, k, stride, pad)
 
 
 def deconv_forward(wb, x, wname, bname, k, stride, pad, act):
-    """ConvTranspose2d(k, stride, padding=pad, output_padding=stride-1) on NHWC.  The parameter
-    [Cin, Cout, k, k] lies in the arena as [Cin][k][k][Cout] = the weight of the stride-`stride`
-    convolution this layer is the data gradient of, so the forward pass is sdmi_igemm on the
-    flipped/transposed operand with virtual zero insertion (exactly GemmFn's dgrad launch)."""
+    """ConvTranspose2d(k, stride, padding=pad, output_padding=stride-1) on NHWC: sdmi_igemm on the flipped/transposed
+    operand with virtual zero insertion (exactly GemmFn's dgrad launch, plus bias and activation; no residual)."""
     dt = x.dtype
-    w = wb.w(wname, dt)                           # [Cin][k*k*Cout]
-    B, H, W_, Cin, Cout, Ho, Wo = _deconv_geom(x, w, k, stride, pad)
-    wd = wb.wd(wname, dt, k, k, Cout)             # [Cout][k'][k'][Cin]
-    y = torch.empty((B, Ho, Wo, Cout), dtype=dt, device=x.device)
-    call('sdmi_igemm', _st(), a=_p(x), w=_p(wd), out=_p(y), bias=_p(wb.b(bname)), dtype=_DT[dt],
-         out_dtype=_DT[dt], M=B * Ho * Wo, N=Cout, K=k * k * Cin, lda=Cin, ldw=k * k * Cin, ldc=Cout,
-         B=B, H=H, W=W_, Cin=Cin, Ho=Ho, Wo=Wo, KH=k, KW=k, stride=1, pad_t=k - 1 - pad,
-         pad_l=k - 1 - pad, ups=0, act=_lib.ACT[act], alpha=1.0, split_k=1, batch=1,
-         zins=(stride if stride > 1 else 0))
+    P = _deconv_problem(wb, x, wname, k, stride, pad)
+    wd = wb.wd(wname, dt, k, k, P.Cin)            # [Cout][k'][k'][Cin]
+    y = torch.empty((P.B, P.H, P.W, P.Cin), dtype=dt, device=x.device)
+    call('sdmi_igemm', _st(), a=_p(x), w=_p(wd), out=_p(y), bias=_p(wb.b(bname)), split_k=1,
+         **dict(P.dgrad_fields(), act=_lib.ACT[act], ldr=0))
     return y
 
 
@@ -2618,7 +2329,8 @@ class DeconvFn(torch.autograd.Function):
         dt = x.dtype
         dy = dy.contiguous()
         w = wb.w(wname, dt)
-        B, H, W_, Cin, Cout, Ho, Wo = _deconv_geom(x, w, k, stride, pad)
+        P = _deconv_problem(wb, x, wname, k, stride, pad)
+        Cout = P.Cin
         if act:                                   # relu: act'(z) from the output
             dz = torch.empty_like(dy)
             call('sdmi_act_bwd', _st(), x=_p(y), dy=_p(dy), dx=_p(dz), dtype=_DT[dt],
@@ -2629,17 +2341,12 @@ class DeconvFn(torch.autograd.Function):
         dx = ops.conv2d(dz, w, None, kh=k, kw=k, stride=stride, pad=(pad, pad, pad, pad)) \
             if ctx.needs_input_grad[0] else None
         # weight gradient: roles swapped (A = dz gathered with the stride, "dY" = x)
-        M, N, K = B * H * W_, Cin, k * k * Cout
-        mt = 64 if dt == torch.bfloat16 else 32
-        tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        splits = max(1, min((192 + tiles - 1) // tiles, M // (8 * mt), 512))
-        ws = torch.empty((splits * (N * K + N),), dtype=torch.float32, device=x.device)
-        call('sdmi_wgrad', _st(), a=_p(dz), dy=_p(x), dw=_p(_grads_of(wb, wname)), dbias=0,
-             workspace=_p(ws), dtype=_DT[dt], M=M, N=N, K=K, lda=Cout, ldy=Cin, B=B, H=Ho, W=Wo,
-             Cin=Cout, Ho=H, Wo=W_, KH=k, KW=k, stride=stride, pad_t=pad, pad_l=pad, ups=0,
-             splits=splits, accumulate=1)
+        splits = bwd.standalone_splits(P)
+        ws = torch.empty((splits * (P.N * P.K + P.N),), dtype=torch.float32, device=x.device)
+        call('sdmi_wgrad', _st(), a=_p(dz), dy=_p(x), dw=_p(_grads_of(wb, wname)), dbias=0, workspace=_p(ws),
+             splits=splits, accumulate=1, **P.wgrad_fields())
         # bias gradient: column sums of dz in 1024-row chunks, folded into the arena
-        rows = B * Ho * Wo
+        rows = P.B * P.H * P.W
         chunk = 1024 if rows % 1024 == 0 else rows
         part = torch.empty((rows // chunk, Cout), dtype=torch.float32, device=x.device)
         call('sdmi_rowgroup_sum', _st(), x=_p(dz), out=_p(part), dtype=_DT[dt], groups=rows // chunk,

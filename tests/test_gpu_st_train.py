@@ -227,7 +227,7 @@ def test_fused_backward_data_path_matches_the_per_layer_kernels(name, hw, B, n_s
         kern.StBlockFn.capture = {}
         try:
             with torch.no_grad():
-                wb._join_queued = True            # (outside an autograd pass: the join below is called by hand)
+                wb.join_by_hand()                 # (outside an autograd pass: the join below is called by hand)
                 if fused:
                     dx, dkv = kern.StBlockFn.backward_fused(wb, n, heads, x, kv, sv, dout, rows)
                 else:

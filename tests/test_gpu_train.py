@@ -928,6 +928,49 @@ def test_pair_backward_equals_side_stream_backward():
     assert rel < 1e-2, rel
 
 
+def test_pending_fold_precedes_a_side_stream_use_of_the_same_parameter():
+    """One bf16 linear parameter with bias (x [1024, 128], W [128, 128]: the readout fixture at slot_size 64, 128
+    features) used twice in one backward.  The first use (need_dx) takes the pair launch with 64-wide dW tiles and four
+    M-splits, so its fold is pending; the second (no dx) runs one split on the parameter's side stream straight into the
+    arena.  bwd.GradSchedule folds before the second writer starts: weight and bias gradients equal, bit for bit, the
+    same two uses with a join between them."""
+    from slotdiffusion_amd import bwd
+    from slotdiffusion_amd.kern import GemmFn, _grads_of, _n_cus
+    from tests import readout_ref as R
+    m = R.build(slot_size=64, feats_dim=128).cuda()
+    m.set_compute_dtype('bf16')
+    wb = m.bank()
+    lin = (0, 0, 1, (0, 0, 0, 0), False)
+    g = torch.Generator().manual_seed(11)
+    x1, dy1, x2, dy2 = (torch.randn(1024, 128, generator=g).bfloat16().cuda() for _ in range(4))
+    # the planned paths first: a retuning that changes them must fail here, not make the comparison vacuous
+    P = bwd.LayerProblem.of(x1, dy1, lin, torch.bfloat16, 128)
+    inputs = dict(direct=True, has_bias=True, bias_dst=True, dalias_cols=None, n_cus=_n_cus(x1.device), pair_bwd=wb.pair_bwd)
+    first, second = bwd.plan_layer(P, need_dx=True, **inputs), bwd.plan_layer(P, need_dx=False, **inputs)
+    assert first.path == 'pair' and (first.pair.wgrad_tile, first.pair.splits) == (64, 4), first
+    assert (second.path, second.splits) == ('side', 1) and wb.overlap_wgrad, second
+    names = ('linear1.weight', 'linear1.bias')
+    ga = m.grad_arena()
+
+    def run(join_between):
+        ga.zero_()
+        with torch.no_grad():
+            wb.join_by_hand()                      # (outside an autograd pass)
+            GemmFn.core(wb, x1, dy1, *names, lin, True)
+            assert (wb.sched._pfold is not None) and wb.sched._pfold[0]['splits'] == 4
+            if join_between:
+                wb.join()
+                wb.join_by_hand()
+            GemmFn.core(wb, x2, dy2, *names, lin, False)
+            wb.join()
+        torch.cuda.synchronize()
+        return [_grads_of(wb, n).clone() for n in names]
+    (w0, b0), (w1, b1) = run(False), run(True)
+    ref_w = dy1.float().t() @ x1.float() + dy2.float().t() @ x2.float()
+    assert float((w1.view(128, 128).cpu() - ref_w.cpu()).norm() / ref_w.norm()) < 1e-5        # (the compared gradients are the layer's, not zeros)
+    assert torch.equal(w0, w1) and torch.equal(b0, b1)
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_layernorm_and_gemm_fanout(dtype):
     """LayerNormFn / GemmFn alias outputs: the residual branch's gradient is summed inside the

@@ -9,7 +9,9 @@ from tests import common as C
 
 def test_library_exports_every_declared_symbol():
     structs, funcs, enums = _lib.parse_header()
-    assert len(funcs) >= 25 and 'sdmi_igemm' in funcs and 'sdmi_slot_attention' in funcs
+    assert len(funcs) >= 25 and 'sdmi_igemm' in funcs and 'sdmi_slot_attention' in funcs and 'sdmi_wgrad_kernel' in funcs
+    assert [enums[k] for k in ('SDMI_WGRAD_KERNEL_IGEMM', 'SDMI_WGRAD_KERNEL_C64', 'SDMI_WGRAD_KERNEL_HALO',
+                               'SDMI_WGRAD_KERNEL_F32_T128', 'SDMI_WGRAD_KERNEL_F32_T64')] == [0, 1, 2, 3, 4]
     L = _lib.lib()                       # raises if the .so or any declared symbol is missing
     assert L.sdmi_version() == 100
     for name in funcs:

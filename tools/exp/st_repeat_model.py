@@ -19,7 +19,7 @@ for name, hw, B, slots, rows in (('input_blocks.4.1', 16, 64, 7, 64), ('input_bl
         with torch.no_grad():
             out, sv = kern.StBlockFn.run_forward(wb, x, kv, n, heads, rows)
             ga.zero_()
-            wb._join_queued = True
+            wb.join_by_hand()
             dx, dkv = kern.StBlockFn.backward_fused(wb, n, heads, x, kv, sv, dout, rows)
             wb.join()
         torch.cuda.synchronize()
