@@ -148,6 +148,27 @@ int sdmi_igemm_split_plan(const SdmiGemmArgs* a, void* stream);
  * (sdmi_igemm_split_plan), every other field as passed to sdmi_igemm.  Sums the partials in slice order
  * and applies alpha / bias / rowvec / residual / act -> out. */
 int sdmi_splitk_finish(const SdmiGemmArgs* a, void* stream);
+/* Host-side record, no launch: the kernel instantiation the LAST sdmi_igemm call of this process launched (0 before
+ * the first; sdmi_splitk_finish and the split-K second stage leave it alone), so that a test can assert which kernel
+ * served it.  Packed as
+ *   bits  0.. 3  family (SDMI_ROUTE_*)
+ *   bits  4.. 6  BM / 64         bits 7.. 9  BN / 64            (output tile; halo: 256 x 128, c64: 256 x 64 = 4 rows of 64 pixels)
+ *   bits 10..12  CFG: K tile bytes / 64 (1 or 2);  DMA / SYM: LDS stages (2..4);  0 otherwise
+ *   bits 13..14  MODE (0 generic gather, 1 1x1 / linear, 2 plain convolution)
+ *   bit  15      extra sources (a2 / a3) instantiation
+ *   bits 16..18  EPI (bit 0 LayerNorm fold, bit 1 GEGLU, bit 2 softmax8)
+ *   bits 19..23  K split used (1 = none)
+ *   bits 24..26  HALO: LOGW (4, 5, 6)
+ *   bit  27      DMA: eight loader waves (else four) */
+enum {
+  SDMI_ROUTE_NONE = 0,
+  SDMI_ROUTE_CFG = 1,      /* igemm_kernel (igemm_kernel_tall for 256-row tiles): register-staged loaders */
+  SDMI_ROUTE_DMA = 2,      /* igemm_dma_kernel: LDS-DMA loader waves */
+  SDMI_ROUTE_SYM = 3,      /* igemm_sym_kernel: symmetric waves */
+  SDMI_ROUTE_HALO = 4,     /* igemm_halo_kernel: 3x3, activation patch staged once per 64-channel chunk */
+  SDMI_ROUTE_C64 = 5       /* conv3x3_c64_kernel: direct 3x3, 64 input channels */
+};
+int sdmi_igemm_last_route(void);
 
 /* wgrad: dW[n][kh][kw][ci] = sum_m dY[m][n] * A[m][(kh,kw,ci)]  (fp32 output, [N][K] like W).
  * Replaces the weight-gradient half of Conv2d/Linear backward (torch autograd in the reference). */

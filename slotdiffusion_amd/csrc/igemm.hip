@@ -30,6 +30,21 @@
 
 #include "igemm_body.h"
 #include "epi_rows.h"
+
+// sdmi_igemm_last_route (sdmi.h): every launch site stores the instantiation it is about to launch -- plain host
+// stores, read back packed; the split-K second stage does not touch it
+namespace {
+struct IgemmRoute { int family, bm, bn, kt, mode, xs, epi, split, logw, lw8; };
+IgemmRoute g_route;
+inline void note_route(int family, int bm, int bn, int kt, int mode, bool xs, int epi, int split, int logw = 0,
+                       bool lw8 = false) {
+  g_route.family = family; g_route.bm = bm; g_route.bn = bn; g_route.kt = kt; g_route.mode = mode;
+  g_route.xs = xs; g_route.epi = epi; g_route.split = split; g_route.logw = logw; g_route.lw8 = lw8;
+}
+}  // namespace
+// (igemm_halo.hip is its own translation unit)
+void sdmi_note_route_halo(int logw, int nj) { note_route(SDMI_ROUTE_HALO, 256, 64 * nj, 0, 2, false, 0, 1, logw); }
+
 #include "igemm_sym.h"
 
 // 3x3 stride-1 convolution with the activation patch staged once per 64-channel chunk (igemm_halo.h)
@@ -586,6 +601,7 @@ int launch_cfg(const SdmiGemmArgs& p, int split_k, int hw_shift, hipStream_t st)
   cap = cap < 8 ? 8 : (cap & ~7);          // multiple of 8: a virtual block id keeps its XCD
   const int nwg = tiles_m * tiles_n;
   dim3 grid(nwg <= cap ? nwg : cap, ny);
+  note_route(SDMI_ROUTE_CFG, BM, BN, BKB / 64, MODE, XS, EPI, split_k);
   hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, q, tiles_m, tiles_n, ktps, hw_shift);
   int rc = sdmi_check_launch("igemm");
   if (rc) return rc;
@@ -625,6 +641,7 @@ int launch_dma(const SdmiGemmArgs& p, int hw_shift, hipStream_t st, int split_k 
   cap = cap < 8 ? 8 : (cap & ~7);
   const int nwg = tiles_m * tiles_n;
   dim3 grid(nwg <= cap ? nwg : cap, ny);
+  note_route(SDMI_ROUTE_DMA, BM, BN, NSTAGE, MODE, XS, EPI, split_k, 0, LW == 8);
   hipLaunchKernelGGL(kern, grid, dim3(threads), smem, st, q, tiles_m, tiles_n, ktps, hw_shift);
   int rc = sdmi_check_launch("igemm (lds-dma)");
   if (rc) return rc;
@@ -755,6 +772,7 @@ int dispatch(const SdmiGemmArgs& p, hipStream_t st, bool plan_only = false) {
     int grid = device_cus();
     const long long n_tiles = (long long)p.B * (p.H / 4) * (p.W / 64);
     if (grid > n_tiles) grid = (int)n_tiles;
+    note_route(SDMI_ROUTE_C64, 256, 64, 0, 2, false, 0, 1);
     hipLaunchKernelGGL(conv3x3_c64_kernel<false>, dim3(grid), dim3(256), D33_SMEM, st, q, hw_shift);
     return sdmi_check_launch("igemm (direct 3x3 c64)");
   }
@@ -978,6 +996,12 @@ extern "C" int sdmi_igemm_split_plan(const SdmiGemmArgs* a, void*) {
   if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0) return 1;
   if (a->dtype == SDMI_FP8) return dispatch<fp8_t>(*a, nullptr, true);
   return a->dtype == SDMI_BF16 ? dispatch<bf16_t>(*a, nullptr, true) : dispatch<float>(*a, nullptr, true);
+}
+
+extern "C" int sdmi_igemm_last_route(void) {
+  const IgemmRoute& r = g_route;
+  return r.family | (r.bm / 64) << 4 | (r.bn / 64) << 7 | r.kt << 10 | r.mode << 13 | r.xs << 15 | r.epi << 16 |
+         r.split << 19 | r.logw << 24 | r.lw8 << 27;
 }
 
 extern "C" int sdmi_splitk_finish(const SdmiGemmArgs* a, void* stream) {

@@ -36,6 +36,8 @@
 #include "igemm_body.h"
 #include "epi_rows.h"
 
+void sdmi_note_route_halo(int logw, int nj);      // igemm.hip: the record behind sdmi_igemm_last_route (sdmi.h)
+
 namespace {
 
 // LOGW: log2 of the tile width = the image width (16 / 32 / 64 columns), or 6 on images of a multiple of 64 columns.  NJ: 32-column blocks per wave -- 2: 256 x 128 tiles (64 x 64
@@ -339,6 +341,7 @@ int launch_halo(const SdmiGemmArgs& p, int hw_shift, hipStream_t st, int n_cu) {
   const int tiles_m = p.M / 256, tiles_n = (p.N + 64 * NJ - 1) / (64 * NJ);
   int cap = n_cu < 8 ? 8 : (n_cu & ~7);
   const int nwg = tiles_m * tiles_n;
+  sdmi_note_route_halo(LOGW, NJ);
   hipLaunchKernelGGL(kern, dim3(nwg <= cap ? nwg : cap), dim3(512), smem, st, q, tiles_m, tiles_n, hw_shift);
   return sdmi_check_launch("igemm (3x3 halo ping-pong)");
 }

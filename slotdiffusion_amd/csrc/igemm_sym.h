@@ -257,6 +257,7 @@ int launch_sym(const SdmiGemmArgs& p, int hw_shift, hipStream_t st, int n_cu, in
   int cap = n_cu * (smem <= 80 * 1024 ? 2 : 1) / split_k;
   cap = cap < 8 ? 8 : (cap & ~7);
   const int nwg = tiles_m * tiles_n;
+  note_route(SDMI_ROUTE_SYM, 128, 128, NSTAGE, MODE, XS, 0, split_k);
   hipLaunchKernelGGL(kern, dim3(nwg <= cap ? nwg : cap, split_k), dim3(512), smem, st, q, tiles_m, tiles_n, hw_shift, ktps);
   return sdmi_check_launch("igemm (symmetric waves)");
 }

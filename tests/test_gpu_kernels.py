@@ -71,7 +71,7 @@ CONV_CASES = [
     (1, 896, 384, 8, 3, 1, (1, 1, 1, 1), False, 'bias'),             # non power-of-two Cin
     (1, 960, 64, 4, 3, 1, (1, 1, 1, 1), False, 'bias'),              # 16 K-splits of 135 K tiles: the last one is empty
     # LDS-DMA kernels (>= 192 tiles of 256x128, or of 128x128 when M is too small for that)
-    (48, 64, 128, 32, 3, 1, (1, 1, 1, 1), False, 'bias,rowvec,res,silu'),   # 256x128, 3 stages
+    (48, 64, 128, 32, 3, 1, (1, 1, 1, 1), False, 'bias,rowvec,res,silu'),   # bf16: 3x3 halo kernel (W = 32); fp32: 128x128 igemm_kernel
     (25, 128, 192, 30, 3, 1, (1, 1, 1, 1), False, 'bias'),           # 128x128 x4 stages, ragged M / N
     (48, 64, 128, 32, 5, 1, (2, 2, 2, 2), False, 'bias'),            # 5x5 taps
     (48, 64, 136, 64, 3, 2, (1, 1, 1, 1), False, 'bias,res'),        # stride 2, ragged N
