@@ -1085,6 +1085,55 @@ typedef struct {
 } SdmiVqBwdArgs;
 int sdmi_vq_bwd(const SdmiVqBwdArgs* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SAVi slot transition: ResidualMLPPredictor and RNNPredictorWrapper (video_based/models/predictor.py:47-73,
+ * 76-135; chosen in savi.py:320-347).  The wrapper's nn.LSTM sees the B N slot rows as one batch of independent rows
+ * (predictor.py:116-117), so every kernel here is row-wise.
+ * ------------------------------------------------------------------------------------------ */
+/* One LSTM step on gate pre-activations z = W_ih u + b_ih + W_hh h_prev + b_hh, [R][4H] fp32 with row pitch ldz, gate
+ * order i, f, g, o (replaces the cell arithmetic inside nn.LSTM, predictor.py:116-117):
+ *   c = sigmoid(z_f) c_prev + sigmoid(z_i) tanh(z_g),   h = sigmoid(z_o) tanh(c)          h, c [R][H] fp32, dense
+ * c_prev == NULL means zeros (the step after a reset, predictor.py:132-135); its row pitch is ldcp.
+ * gates != NULL: also the ACTIVATED gates [R][4H] (dense) that sdmi_lstm_cell_bwd reads. */
+typedef struct {
+  const float* z; const float* c_prev; float* h; float* c; float* gates;
+  int R, H, ldz, ldcp;
+} SdmiLstmCellArgs;
+int sdmi_lstm_cell(const SdmiLstmCellArgs* a, void* stream);
+/* Backward of sdmi_lstm_cell.  dh [R][H] (gradient of h), dc_next [R][H] or NULL (gradient that reaches c from the next
+ * step), the stored gates [R][4H], c_prev (NULL = zeros, pitch ldcp) and c [R][H] -> dz [R][4H] and dc_prev [R][H]
+ * (both dense).  The GEMM's weight and data gradients are sdmi_wgrad / sdmi_igemm on dz, as for every linear layer. */
+typedef struct {
+  const float* dh; const float* dc_next; const float* gates; const float* c_prev; const float* c;
+  float* dz; float* dc_prev;
+  int R, H, ldcp;
+} SdmiLstmCellBwdArgs;
+int sdmi_lstm_cell_bwd(const SdmiLstmCellBwdArgs* a, void* stream);
+
+/* The whole transition of one frame as ONE launch (bf16 operands, inference): per tile of 16 slot rows
+ *   mode & SDMI_PRED_MLP  (predictor.py:65-73):  xn = LayerNorm(x);  res = norm_first ? xn : x;
+ *                                                 u = W2 relu(W1 xn + b1) + b2 + res        (else u = x)
+ *   mode & SDMI_PRED_RNN  (predictor.py:113-118): z = [W_ih | W_hh] [u | h_prev] + b_ih + b_hh;  the cell update of
+ *                                                 sdmi_lstm_cell;  y = W_o h + b_o            (else y = u)
+ * x [R][D] fp32 (pitch ldx; with SDMI_PRED_RNN alone it is the transformer predictor's output), h_prev / c_prev [R][H]
+ * fp32 (pitch ldh; NULL = zeros), y [R][D], h / c [R][H] fp32 dense.  MFMA operands are rounded to bf16 once where
+ * they feed a product (xn, the hidden layer, u, h_prev, h); accumulators, LayerNorm, the residual, the cell state and
+ * every output are fp32.  The weights come packed in MFMA B-fragment order (kern.pred_pack_index): for output-row
+ * chunk n (16 rows) and k step s (32 columns) the 64 lanes' 8 elements, lane l = row 16 n + l % 16, columns
+ * 32 s + 8 (l / 16) ..; the gate matrix per hidden chunk and k step as the i, f, g, o fragments.
+ *   w1p [2D x D], w2p [D x 2D], wgp [4H x (D + H)], wop [D x H];  b1 [2D], b2 [D], bg [4H] = b_ih + b_hh, bo [D] fp32.
+ * D and H multiples of 32, D <= 256, H <= 512 (kern.pred_step_covers). */
+enum { SDMI_PRED_MLP = 1, SDMI_PRED_RNN = 2 };
+typedef struct {
+  const float* x; const float* h_prev; const float* c_prev;
+  float* y; float* h; float* c;
+  const float* ln_g; const float* ln_b;
+  const void* w1p; const float* b1; const void* w2p; const float* b2;
+  const void* wgp; const float* bg; const void* wop; const float* bo;
+  int R, D, H, ldx, ldh, mode, norm_first; float eps;
+} SdmiPredStepArgs;
+int sdmi_pred_step(const SdmiPredStepArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,9 +137,104 @@ def transformer_predictor(K, x, num_layers, num_heads, name='predictor'):
 
 
 # ------------------------------------------------------------------------------------------
+# SAVi slot transition, the other two families (video_based/models/predictor.py:47-73 ResidualMLPPredictor,
+# 76-135 RNNPredictorWrapper; savi.py:320-347 chooses)
+# ------------------------------------------------------------------------------------------
+class PredictorState:
+    """Host-side bookkeeping of RNNPredictorWrapper (predictor.py:94-111, 132-135; savi.py:453-455): the (h, c) pair
+    carried from frame to frame, the count of calls since the last reset, and the stop-gradient every `sg_every` calls.
+    Holds whatever the transition hands it (tensors, or anything with `.detach()`); touches no device."""
+
+    def __init__(self, sg_every=None):
+        self.sg_every = sg_every
+        self.reset()
+
+    def reset(self):
+        """predictor.py:132-135."""
+        self.step = 0
+        self.hidden = None
+
+    def begin_forward(self, prev_slots):
+        """savi.py:453-455: a forward that starts without previous slots starts a new video."""
+        if prev_slots is None:
+            self.reset()
+
+    def cuts(self):
+        """predictor.py:103-104: whether the NEXT call detaches its input and the state."""
+        return self.sg_every is not None and self.step % self.sg_every == 0 and self.step > 0
+
+    def enter(self, x):
+        """-> (x, hidden) for the next call, both detached when the call is a cut (predictor.py:103-111)."""
+        if self.cuts():
+            x = x.detach()
+            if self.hidden is not None:
+                self.hidden = tuple(h.detach() for h in self.hidden)
+        return x, self.hidden
+
+    def leave(self, hidden):
+        """predictor.py:116-119: keep the new state, count the call."""
+        self.hidden = hidden
+        self.step += 1
+
+
+def residual_mlp_predictor(K, x, name, norm_first=True):
+    """predictor.py:65-73 on rows x [R, D]: out = mlp(LN(x)) + (LN(x) if norm_first else x); channels [D, 2D, D]."""
+    if norm_first:
+        n = res = K.ln(x, f'{name}.ln')
+    else:
+        n, res = K.ln_fan(x, f'{name}.ln')
+    hid = K.linear(n, f'{name}.mlp.0.weight', f'{name}.mlp.0.bias', act='relu')
+    return K.linear(hid, f'{name}.mlp.2.weight', f'{name}.mlp.2.bias', residual=res)
+
+
+def lstm_wrapper(K, u, state, name):
+    """predictor.py:113-118 behind the base predictor: one nn.LSTM step on the rows u [R, D] (the reference views them
+    as [1, R, D]: R independent rows) and the out projector.  state = (h, c) fp32 or None (zeros) -> (y fp32, (h, c)).
+    z = W_ih u + b_ih + W_hh h + b_hh is two sdmi_igemm calls, the second adding onto the first."""
+    r = f'{name}.rnn'
+    f32 = torch.float32
+    H = K.wb.t[f'{r}.weight_hh_l0'].shape[1]
+    h_prev, c_prev = state if state is not None else (ops.zeros((u.shape[0], H), f32, u.device), None)
+    gi = K.linear(u, f'{r}.weight_ih_l0', f'{r}.bias_ih_l0', out_dtype=f32)
+    z = K.linear(K.cast(h_prev, u.dtype), f'{r}.weight_hh_l0', f'{r}.bias_hh_l0', residual=gi, out_dtype=f32)
+    h, c = K.lstm_cell(z, c_prev)
+    y = K.linear(K.cast(h, u.dtype), f'{name}.out_projector.weight', f'{name}.out_projector.bias', out_dtype=f32)
+    return y, (h, c)
+
+
+def slot_transition(K, x, pred_dict, state, name='predictor'):
+    """The slot transition of SAVi / SAViDiffusion (savi.py:320-347) on x [B, N, D] fp32 -> [B, N, D] fp32; `state` is
+    the model's PredictorState (used with pred_rnn only).  Inference on a bf16 model inside the kernel's geometry: ONE
+    sdmi_pred_step launch (behind the transformer's launches when that is the base predictor); otherwise the composed
+    chain of K.ln / K.linear / K.lstm_cell launches, which records gradients under KernGrad."""
+    B, N, D = x.shape
+    mlp, rnn = spec.pred_is_mlp(pred_dict), bool(pred_dict.get('pred_rnn', False))
+    base = spec.pred_base_name(pred_dict, name)
+    hidden = None
+    if rnn:
+        x, hidden = state.enter(x)
+    if not mlp:
+        x = transformer_predictor(K, x, pred_dict['pred_num_layers'], pred_dict['pred_num_heads'], name=base)
+        if not rnn:
+            return x
+    rows = x.reshape(B * N, D)
+    norm_first = bool(pred_dict.get('pred_norm_first', True))
+    fused = K.pred_step(rows, base if mlp else None, name if rnn else None, norm_first, hidden)
+    if fused is not None:
+        y, hidden = fused
+    else:
+        y = residual_mlp_predictor(K, rows, base, norm_first) if mlp else rows
+        if rnn:
+            y, hidden = lstm_wrapper(K, y, hidden, name)
+    if rnn:
+        state.leave(hidden)
+    return y.view(B, N, D)
+
+
+# ------------------------------------------------------------------------------------------
 # SlotFormer rollout: autoregressive transformer over a sliding window of slots (vp_vqa/models/slotformer.py:83-126)
 # ------------------------------------------------------------------------------------------
-ROLLOUT_TILE = 64          # token rows per workgroup of the fused layer (csrc/rollout_layer.hip)
+ROLLOUT_TILE = 64         # token rows per workgroup of the fused layer (csrc/rollout_layer.hip)
 
 
 def rollout_pos(K, name, T, N, Lp):

@@ -221,6 +221,54 @@ def readout_pack_index(C, F, dtype, device='cpu'):
     return _READOUT_INDEX[key]
 
 
+# SAVi slot transition (ResidualMLPPredictor / RNNPredictorWrapper) as ONE sdmi_pred_step launch wherever the kernel
+# covers the geometry (pred_step_covers) on a bf16 model that records no gradient; the rest, and everything with this off
+# (tests, tools/bench_pred.py), runs the composed chain engine.slot_transition.  Not a policy switch.
+_PRED_FUSED = True
+_PRED_INDEX = {}
+
+
+def pred_step_covers(D, H):
+    """Geometry of sdmi_pred_step (sdmi.h): both multiples of 32 inside its LDS budget.  H = 0: no LSTM wrapper."""
+    return 32 <= D <= 256 and D % 32 == 0 and (H == 0 or (32 <= H <= 512 and H % 32 == 0))
+
+
+def pred_pack_index(N, K, gates=1, device='cpu'):
+    """int64 [N * K]: position in a weight [N, K] (flat) of every element of its packed operand for sdmi_pred_step
+    (sdmi.h) -- per chunk of 16 output rows and k step of 32, the MFMA B fragment lane by lane (lane l: row l % 16,
+    columns 8 (l // 16) ..).  gates = 4: the LSTM's [4H, K]; a chunk is 16 hidden units and holds the i, f, g, o
+    fragments of every k step side by side."""
+    key = (N, K, gates, str(device))
+    if key not in _PRED_INDEX:
+        ar = lambda n: torch.arange(n, device=device)
+        per = N // gates
+        c, s, g, l, e = torch.meshgrid(ar(per // 16), ar(K // 32), ar(gates), ar(64), ar(8), indexing='ij')
+        row = g * per + 16 * c + l % 16
+        col = 32 * s + 8 * (l // 16) + e
+        _PRED_INDEX[key] = (row * K + col).reshape(-1)
+    return _PRED_INDEX[key]
+
+
+def pred_pack(W, base, wrap, device=None):
+    """Operands of sdmi_pred_step out of a {key: tensor} dict: `base` = key prefix of a ResidualMLPPredictor or None,
+    `wrap` = key prefix of the RNNPredictorWrapper's own tensors or None.  Weights are rounded to bf16 and packed
+    (pred_pack_index); [W_ih | W_hh] is one operand over K = D + H and b_ih + b_hh one vector."""
+    out = {}
+    dev = device or next(iter(W.values())).device
+    pk = lambda w, gates=1: w.to(dev).to(torch.bfloat16).reshape(-1)[
+        pred_pack_index(w.shape[0], w.shape[1], gates, dev)].contiguous()
+    f = lambda k: W[k].detach().to(dev).float().contiguous()
+    if base is not None:
+        out.update(ln_g=f(base + '.ln.weight'), ln_b=f(base + '.ln.bias'), w1p=pk(f(base + '.mlp.0.weight')),
+                   b1=f(base + '.mlp.0.bias'), w2p=pk(f(base + '.mlp.2.weight')), b2=f(base + '.mlp.2.bias'))
+    if wrap is not None:
+        wg = torch.cat([f(wrap + '.rnn.weight_ih_l0'), f(wrap + '.rnn.weight_hh_l0')], 1)
+        out.update(wgp=pk(wg, 4), bg=(f(wrap + '.rnn.bias_ih_l0') + f(wrap + '.rnn.bias_hh_l0')).contiguous(),
+                   wop=pk(f(wrap + '.out_projector.weight')), bo=f(wrap + '.out_projector.bias'),
+                   H=wg.shape[0] // 4)
+    return out
+
+
 def st_train_units(C):
     """Unit order of the training kernels' weight streams (csrc/st_train.hip), per wave: lists of
     (matrix key, first row, first k, transposed).  Forward: a = [proj_in | q | k | v], b = [to_out | q2 | to_out2 | per
@@ -659,6 +707,15 @@ class WeightBank:
                 src = self._flat(name, dtype)
                 idx = readout_pack_index(C2 // 2, F, dtype, src.device)
                 self.cache[key] = src.reshape(-1)[idx].contiguous()
+        return self.cache[key]
+
+    def pred_step_weights(self, base, wrap):
+        """Packed operands of the fused slot transition (pred_pack) from the master weights, rounded to bf16 as the
+        shadow arena rounds them.  Weight preparation, cached until the weights change."""
+        key = ('pred_step', base, wrap)
+        if key not in self.cache:
+            with torch.no_grad():
+                self.cache[key] = pred_pack(self.t, base, wrap)
         return self.cache[key]
 
     # ---- weight streams of the fused SpatialTransformer TRAINING kernels (sdmi.h: sdmi_st_train_fwd, sdmi_st_pack)
@@ -1112,6 +1169,24 @@ class Kern:
 
     def cast(self, x, dtype):
         return x if x.dtype == dtype else ops.act(x, None, dtype)
+
+    def lstm_cell(self, z, c_prev):
+        return ops.lstm_cell(z, c_prev)[:2]
+
+    def pred_step(self, x, base, wrap, norm_first, state):
+        """The whole slot transition as ONE sdmi_pred_step launch: x [R, D] fp32, `base` = key prefix of the MLP
+        predictor or None (x is then the transformer predictor's output), `wrap` = key prefix of the LSTM wrapper or
+        None, state = (h, c) | None -> (y, (h, c) | None); None when the launch does not apply (the caller runs the
+        composed chain): fp32 model, geometry outside pred_step_covers."""
+        W = self.wb.t
+        H = W[wrap + '.rnn.weight_hh_l0'].shape[1] if wrap else 0
+        if not (_PRED_FUSED and self.wb.dtype == torch.bfloat16 and x.dtype == torch.float32 and
+                pred_step_covers(x.shape[-1], H)):
+            return None
+        mode = (ops.PRED_MLP if base else 0) | (ops.PRED_RNN if wrap else 0)
+        h, c = state if state is not None else (None, None)
+        y, h, c = ops.pred_step(x, self.wb.pred_step_weights(base, wrap), mode, norm_first, h, c)
+        return y, ((h, c) if wrap else None)
 
     def cast_pad(self, x, dtype, cols, ldd):
         """First `cols` channels of x [..., ld] -> dtype [..., ldd] (zero padded)."""
@@ -1996,6 +2071,29 @@ class GruGatesFn(torch.autograd.Function):
         return dgi, dgh, dh
 
 
+class LstmCellFn(torch.autograd.Function):
+    """One LSTM step on gate pre-activations (sdmi_lstm_cell): (z [R, 4H], c_prev [R, H] | None) -> (h, c).  The
+    backward is ONE sdmi_lstm_cell_bwd on the stored activated gates; a frame's dc_prev is the previous frame's dc."""
+
+    @staticmethod
+    def forward(ctx, z, c_prev):
+        h, c, gates = ops.lstm_cell(z, c_prev, want_gates=True)
+        ctx.has_prev = c_prev is not None
+        ctx.save_for_backward(*((gates, c, c_prev) if ctx.has_prev else (gates, c)))
+        ctx.set_materialize_grads(False)
+        return h, c
+
+    @staticmethod
+    def backward(ctx, dh, dc):
+        if dh is None and dc is None:
+            return None, None
+        gates, c = ctx.saved_tensors[:2]
+        c_prev = ctx.saved_tensors[2] if ctx.has_prev else None
+        dh = ops.zeros(c.shape, torch.float32, c.device) if dh is None else dh.contiguous()
+        dz, dcp = ops.lstm_cell_bwd(dh, None if dc is None else dc.contiguous(), gates, c_prev, c)
+        return dz, (dcp if ctx.has_prev else None)
+
+
 class AddFn(torch.autograd.Function):
     """y = a + b on our add kernel (both grads are dy)."""
 
@@ -2598,6 +2696,12 @@ class KernGrad(Kern):
 
     def cast(self, x, dtype):
         return x if x.dtype == dtype else CastFn.apply(x, dtype)
+
+    def lstm_cell(self, z, c_prev):
+        return LstmCellFn.apply(z, c_prev)
+
+    def pred_step(self, x, base, wrap, norm_first, state):
+        return None                         # (recording gradients: the composed chain is the training path)
 
     def cast_pad(self, x, dtype, cols, ldd):
         return CastPadFn.apply(x, dtype, cols, ldd)

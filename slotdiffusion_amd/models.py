@@ -818,10 +818,12 @@ class SADiffusion(SlotModelBase):
 
 def _encode_clip(self, img, prev_slots=None):
     """Per-frame Slot Attention recurrence shared by the video models (savi.py:366-397,
-    savi_diffusion.py:169-216): the initial slots of frame t are the transformer predictor's output
-    on frame t-1's slots (the learnt init_latents on the first frame).  -> slots [B,T,N,D],
-    masks [B,T,N,h,w] (train) / [B,T,N,H,W] (eval)."""
+    savi_diffusion.py:169-216): the initial slots of frame t are the slot transition's output (savi.py:320-347:
+    transformer or residual MLP, optionally inside the LSTM wrapper) on frame t-1's slots (the learnt init_latents on
+    the first frame).  A call without prev_slots starts a new video and clears the wrapper's state (savi.py:453-455); a
+    call with them continues it.  -> slots [B,T,N,D], masks [B,T,N,h,w] (train) / [B,T,N,H,W] (eval)."""
     B, T, _, H, W = img.shape
+    self.pred_state.begin_forward(prev_slots)
     grad = self.training and torch.is_grad_enabled()
     Kp = self.KG() if grad else self.K()
     h, w = self.visual_resolution
@@ -833,9 +835,7 @@ def _encode_clip(self, img, prev_slots=None):
             if prev_slots is None:
                 lat = self.init_latents[0]
             else:
-                lat = engine.transformer_predictor(Kp, prev_slots.contiguous(),
-                                                   self.pred_dict['pred_num_layers'],
-                                                   self.pred_dict['pred_num_heads'])
+                lat = engine.slot_transition(Kp, prev_slots.contiguous(), self.pred_dict, self.pred_state)
             tk = tok[:, t].contiguous() if T > 1 else tok[:, 0]
             s, seg = engine.slot_attention(Kp, tk, lat, self.num_iterations, self.eps)
             all_s.append(s)
@@ -859,14 +859,13 @@ class SAViDiffusion(SADiffusion):
 
     def __init__(self, resolution, clip_len, slot_dict, enc_dict, dec_dict, pred_dict,
                  loss_dict=None, eps=1e-6, compute_dtype=None, seed=0):
-        assert pred_dict.get('pred_type', 'transformer') == 'transformer' and \
-            not pred_dict.get('pred_rnn', False), 'hot path covers the transformer predictor'
         self._pred_dict = dict(pred_dict)
         self.clip_len = clip_len
         super().__init__(resolution, slot_dict, enc_dict, dec_dict, loss_dict, eps, compute_dtype,
                          seed)
         self.pred_dict = dict(pred_dict)
         self.pred_dropout = 0.1            # nn.TransformerEncoderLayer default (predictor.py:33-38)
+        self.pred_state = engine.PredictorState(pred_dict.get('pred_sg_every'))
 
     def _make_spec(self, resolution, slot_dict, enc_dict, dec_dict):
         return spec.savi_diffusion(resolution, slot_dict, enc_dict, dec_dict, self._pred_dict)
@@ -996,14 +995,13 @@ class SAVi(SA):
 
     def __init__(self, resolution, clip_len, slot_dict, enc_dict, dec_dict, pred_dict,
                  loss_dict=None, eps=1e-6, compute_dtype=None, seed=0):
-        assert pred_dict.get('pred_type', 'transformer') == 'transformer' and \
-            not pred_dict.get('pred_rnn', False), 'hot path covers the transformer predictor'
         self._pred_dict = dict(pred_dict)
         super().__init__(resolution, slot_dict, enc_dict, dec_dict, loss_dict, eps, compute_dtype,
                          seed)
         self.clip_len = clip_len
         self.pred_dict = dict(pred_dict)
         self.pred_dropout = 0.1            # nn.TransformerEncoderLayer default (predictor.py:33-38)
+        self.pred_state = engine.PredictorState(pred_dict.get('pred_sg_every'))
 
     def _make_spec(self, resolution, slot_dict, enc_dict, dec_dict):
         return spec.savi_model(resolution, slot_dict, enc_dict, dec_dict, self._pred_dict)

@@ -925,3 +925,61 @@ def readout_bwd(slots, w1p, b1, w2, t_star, dlogit, agg, op_dtype, gscale=None, 
          B=B, T=T, N=N, C=C, F=F, agg=_agg(agg), x_dtype=_dt(slots), op_dtype=_DT[op_dtype], accumulate=int(accumulate),
          _meta=dict(flops=4.0 * B * N * C * F, bytes=float(B * N * C * slots.element_size() * (F // 4) + 8 * F * C)))
     return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------
+# SAVi slot transition (sdmi.h: sdmi_lstm_cell / sdmi_lstm_cell_bwd / sdmi_pred_step)
+# ------------------------------------------------------------------------------------------
+PRED_MLP, PRED_RNN = _lib.ENUMS['SDMI_PRED_MLP'], _lib.ENUMS['SDMI_PRED_RNN']
+
+
+def _pitch(t):
+    """Row pitch of a 2-D fp32 view whose rows are contiguous (0 for None)."""
+    if t is None:
+        return 0
+    assert t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1
+    return t.stride(0)
+
+
+def lstm_cell(z, c_prev=None, want_gates=False):
+    """Gate pre-activations z [R, 4H] fp32 (i, f, g, o; rows may be pitched), c_prev [R, H] or None (zeros) ->
+    (h, c, activated gates [R, 4H] | None)."""
+    _need_gpu(z)
+    R, H = z.shape[0], z.shape[1] // 4
+    h = torch.empty((R, H), dtype=torch.float32, device=z.device)
+    c = torch.empty_like(h)
+    gates = torch.empty((R, 4 * H), dtype=torch.float32, device=z.device) if want_gates else None
+    call('sdmi_lstm_cell', _stream(), z=_p(z), c_prev=_p(c_prev), h=_p(h), c=_p(c), gates=_p(gates), R=R, H=H,
+         ldz=_pitch(z), ldcp=_pitch(c_prev))
+    return h, c, gates
+
+
+def lstm_cell_bwd(dh, dc_next, gates, c_prev, c):
+    """-> (dz [R, 4H], dc_prev [R, H]); dc_next / c_prev may be None (zeros)."""
+    _need_gpu(dh, gates, c)
+    R, H = c.shape
+    dz = torch.empty((R, 4 * H), dtype=torch.float32, device=c.device)
+    dcp = torch.empty((R, H), dtype=torch.float32, device=c.device)
+    call('sdmi_lstm_cell_bwd', _stream(), dh=_p(dh), dc_next=_p(dc_next), gates=_p(gates), c_prev=_p(c_prev), c=_p(c),
+         dz=_p(dz), dc_prev=_p(dcp), R=R, H=H, ldcp=_pitch(c_prev))
+    return dz, dcp
+
+
+def pred_step(x, W, mode, norm_first=True, h_prev=None, c_prev=None, eps=1e-5):
+    """The fused transition: x [R, D] fp32 (rows may be pitched), W = dict of the packed bf16 operands and fp32 vectors
+    (kern.pred_pack; keys ln_g ln_b w1p b1 w2p b2 for PRED_MLP, wgp bg wop bo H for PRED_RNN), h_prev / c_prev [R, H]
+    fp32 of one pitch or None (zeros) -> (y [R, D], h, c) fp32; h, c are None without PRED_RNN."""
+    _need_gpu(x)
+    R, D = x.shape
+    rnn = bool(mode & PRED_RNN)
+    H = W['H'] if rnn else 0
+    assert (h_prev is None) == (c_prev is None) and (h_prev is None or _pitch(h_prev) == _pitch(c_prev))
+    y = torch.empty((R, D), dtype=torch.float32, device=x.device)
+    h = torch.empty((R, H), dtype=torch.float32, device=x.device) if rnn else None
+    c = torch.empty_like(h) if rnn else None
+    g = lambda k: _p(W.get(k))
+    call('sdmi_pred_step', _stream(), x=_p(x), h_prev=_p(h_prev), c_prev=_p(c_prev), y=_p(y), h=_p(h), c=_p(c),
+         ln_g=g('ln_g'), ln_b=g('ln_b'), w1p=g('w1p'), b1=g('b1'), w2p=g('w2p'), b2=g('b2'), wgp=g('wgp'), bg=g('bg'),
+         wop=g('wop'), bo=g('bo'), R=R, D=D, H=H, ldx=_pitch(x), ldh=_pitch(h_prev), mode=mode,
+         norm_first=int(bool(norm_first)), eps=eps)
+    return y, h, c

@@ -21,6 +21,8 @@ Reference layouts restated (names only, no code shared):
   VQVAE wrapper ............. video_based/models/vqvae/VQVAE.py:66-82
   DDPM schedule buffers ..... video_based/models/ddpm/ddpm.py:69-131
   TransformerPredictor ...... video_based/models/predictor.py:20-44
+  ResidualMLPPredictor ...... video_based/models/predictor.py:47-61
+  RNNPredictorWrapper ....... video_based/models/predictor.py:76-96
   SlotRollouter ............. vp_vqa/models/slotformer.py:46-81
   PhysionReadout ............ vp_vqa/models/readout.py:39-54
 """
@@ -177,6 +179,44 @@ def transformer_predictor(name, d_model, num_layers, ffn_dim):
         out += linear(f'{l}.linear1', d_model, ffn_dim)
         out += linear(f'{l}.linear2', ffn_dim, d_model)
         out += norm(f'{l}.norm1', d_model) + norm(f'{l}.norm2', d_model)
+    return out
+
+
+def residual_mlp_predictor(name, d):
+    """ResidualMLPPredictor with channels [D, 2D, D] (predictor.py:47-61, savi.py:326-329)."""
+    return norm(f'{name}.ln', d) + linear(f'{name}.mlp.0', d, 2 * d) + linear(f'{name}.mlp.2', 2 * d, d)
+
+
+def rnn_wrapper(name, d, hidden):
+    """nn.LSTM(d, hidden) + out_projector of RNNPredictorWrapper (predictor.py:91-96), behind the base predictor's
+    tensors.  Gate order i, f, g, o; all four LSTM tensors U(+-1/sqrt(hidden))."""
+    out = [_p(f'{name}.rnn.weight_ih_l0', (4 * hidden, d), 'gru', hidden),
+           _p(f'{name}.rnn.weight_hh_l0', (4 * hidden, hidden), 'gru', hidden),
+           _p(f'{name}.rnn.bias_ih_l0', (4 * hidden,), 'gru', hidden),
+           _p(f'{name}.rnn.bias_hh_l0', (4 * hidden,), 'gru', hidden)]
+    return out + linear(f'{name}.out_projector', hidden, d)
+
+
+def pred_is_mlp(pred_dict):
+    """savi.py:320-340: 'mlp' selects ResidualMLPPredictor, anything else the transformer."""
+    return pred_dict.get('pred_type', 'transformer') == 'mlp'
+
+
+def pred_base_name(pred_dict, name='predictor'):
+    """Key prefix of the base predictor: RNNPredictorWrapper holds it as `base_predictor` (predictor.py:91)."""
+    return f'{name}.base_predictor' if pred_dict.get('pred_rnn', False) else name
+
+
+def slot_predictor(slot_dict, pred_dict, name='predictor'):
+    """The slot transition of SAVi / SAViDiffusion (savi.py:320-347) in state_dict order."""
+    d = pred_dict['pred_slot_size'] if 'pred_slot_size' in pred_dict else slot_dict['slot_size']
+    base = pred_base_name(pred_dict, name)
+    if pred_is_mlp(pred_dict):
+        out = residual_mlp_predictor(base, d)
+    else:
+        out = transformer_predictor(base, d, pred_dict['pred_num_layers'], pred_dict['pred_ffn_dim'])
+    if pred_dict.get('pred_rnn', False):
+        out += rnn_wrapper(name, d, slot_dict['slot_mlp_size'])
     return out
 
 
@@ -452,10 +492,7 @@ def sa_model(resolution, slot_dict, enc_dict, dec_dict):
 def savi_model(resolution, slot_dict, enc_dict, dec_dict, pred_dict):
     """Video Slot Attention baseline (registry name 'SAVi', video_based/models/savi.py:117-170):
     the plain-SA tensors followed by the slot transition predictor."""
-    pred = transformer_predictor('predictor', pred_dict['pred_slot_size'] if 'pred_slot_size'
-                                 in pred_dict else slot_dict['slot_size'],
-                                 pred_dict['pred_num_layers'], pred_dict['pred_ffn_dim'])
-    return sa_model(resolution, slot_dict, enc_dict, dec_dict) + pred
+    return sa_model(resolution, slot_dict, enc_dict, dec_dict) + slot_predictor(slot_dict, pred_dict)
 
 
 def sa_diffusion(resolution, slot_dict, enc_dict, dec_dict):
@@ -468,10 +505,7 @@ def savi_diffusion(resolution, slot_dict, enc_dict, dec_dict, pred_dict):
     enc, _, _ = sa_encoder_side(resolution, slot_dict, enc_dict)
     head = [p for p in enc if p.name == 'init_latents' or p.name.startswith('slot_attention.')]
     rest = [p for p in enc if p not in head]
-    pred = transformer_predictor('predictor', pred_dict['pred_slot_size'] if 'pred_slot_size'
-                                 in pred_dict else slot_dict['slot_size'],
-                                 pred_dict['pred_num_layers'], pred_dict['pred_ffn_dim'])
-    return head + rest + ldm('dm_decoder', dec_dict) + pred
+    return head + rest + ldm('dm_decoder', dec_dict) + slot_predictor(slot_dict, pred_dict)
 
 
 def slot_rollouter(name, rollout_dict):
