@@ -4,9 +4,10 @@
 // batch_first=True):  x += out_proj(MHA(LN1(x)));  x += linear2(relu(linear1(LN2(x)))).
 //
 // The layer is st_fused.hip's SpatialTransformer block without GroupNorm, proj_in, the folded cross-attention, GEGLU
-// and proj_out; it has a biased q | k | v and a ReLU feed-forward.  Same two launches, same GEMM core (st_core.h:
-// weights as the A operand of v_mfma_f32_16x16x32_bf16, per-wave weight rings over LDS-DMA with counted vmcnt,
-// LayerNorm folded into the epilogue), same operand layouts:
+// and proj_out; it has a biased q | k | v and a ReLU feed-forward.  Same two launches, built from the same pieces
+// (st_core.h: weights as the A operand of v_mfma_f32_16x16x32_bf16, per-wave weight rings over LDS-DMA with counted
+// vmcnt, LayerNorm folded into the epilogue, the self-attention stage, the row <-> operand buffer copies), same operand
+// layouts:
 //   phase A  x rows -> LDS;  LayerNorm-fold -> q | k | v (+ bias)                                   [B][Lp][3C]
 //   phase B  self-attention of the 64 rows over the sequence's L keys -> out_proj + x -> LayerNorm-fold ->
 //            linear1 + ReLU, hidden chunk (128) by hidden chunk, accumulated straight into linear2 -> + x1
@@ -48,46 +49,18 @@ __global__ __launch_bounds__(512) void rollout_qkv_kernel(SdmiRolloutLayerArgs p
   const int lrow0 = rb * ROWS;                                   // ... within its sequence
 
   StRing<D> rg;
-  rg.rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.wstream_a + (long long)w * G::UA * ST_UNIT), 0,
-                                               G::UA * ST_UNIT, 0x00020000);
-  rg.rs_img = rg.rs_sh;
-  rg.g_iss = 0; rg.n1 = G::UA; rg.n_img = 0; rg.total = G::UA; rg.pos_iss = 0; rg.pos_con = 0;
-  rg.ring = smem + G::RING_OFF + w * D * ST_UNIT;
-  rg.voff = lane * 16;
-#pragma unroll
-  for (int i = 0; i < D; ++i) rg.issue_one();               // weights in flight under the activation load
-
-  // ---- this workgroup's 64 rows into the operand buffer (XOR-swizzled 16-byte chunks, st_fused.hip's layout)
-  {
-    constexpr int VPR = C / 8;                    // vectors per row
-    const bf16_t* xr = (const bf16_t*)p.x + row0 * C;
-    static_assert((ROWS * VPR) % 512 == 0, "whole passes");
-    u32x4 v[ROWS * VPR / 512];
-#pragma unroll
-    for (int it = 0; it < ROWS * VPR / 512; ++it) {
-      const int i = tid + it * 512;
-      const int r = i / VPR, vc = i - r * VPR;
-      v[it] = *reinterpret_cast<const u32x4*>(xr + (long long)r * C + vc * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < ROWS * VPR / 512; ++it) {
-      const int i = tid + it * 512;
-      const int r = i / VPR, vc = i - r * VPR;
-      const int phys = (vc & ~15) | ((vc ^ r) & 15);
-      *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(Y + r * PITCH + phys * 16) = v[it];
-    }
-  }
+  st_ring_init<D>(rg, p.wstream_a, G::UA, smem + G::RING_OFF, lane, w);      // weights in flight under the activation load
+  // ---- this workgroup's 64 rows into the operand buffer
+  st_load_rows_to_y<C, ROWS>((const bf16_t*)p.x + row0 * C, C, Y, tid);
   ST_BARRIER();
 
   int yaddr[4], woff[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) yaddr[j] = l15 * PITCH + ((((4 * j + lg) ^ l15) & 15) * 16);
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+  st_frag_addrs<PITCH>(l15, lg, yaddr, woff);
   float sx[TT], sxx[TT], mean[TT], rstd[TT];
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) sx[tt] = sxx[tt] = 0.f;
 
+  // ---- q | k | v = LayerNorm1(x) W^T + b through the fold; pad rows are written as zeros
   // (epilogue operands are fetched BEFORE the GEMM they follow: st_fused.hip's note on vmcnt order)
   f32x4 acc[NSL][TT], ev0[NSL], ev1[NSL];
 #pragma unroll 1
@@ -158,167 +131,20 @@ __global__ __launch_bounds__(512) void rollout_tail_kernel(SdmiRolloutLayerArgs 
   const int ub = G::UB0 + NHC * G::UCH;                     // units per wave of the stream
 
   // =========================== self-attention: 64 queries x 8 heads over the L real keys ===========================
-  // (st_fused.hip's stage: a wave owns 32 queries of one head, four heads per round; keys >= L masked out)
   unsigned opack[HEADS / 4][8];
-  {
-    const int hs = w >> 1, qh = w & 1;
-    const int ql = lane & 31, hh = lane >> 5;
-    const bf16_t* qkv_seq = (const bf16_t*)p.qkv + (long long)b * S * 3 * C;
-    const int head_bytes = S * (ST_KP + ST_VP);
-    const float sc2 = p.attn_scale * 1.4426950408889634f;
-    const int g4 = lane >> 4, t16 = lane & 15;
-    const bool all_heads = HEADS * head_bytes <= 160 * 1024;
-    const int hb = all_heads ? HEADS : 4;
-    const int nkb = (L + 31) >> 5;                          // 32-key blocks that hold a real key
-    bf16x8 bq[HEADS / 4][2];
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      const bf16_t* qp = (const bf16_t*)p.qkv + (row0 + qh * 32 + ql) * 3 * C + (ri * 4 + hs) * 32 + hh * 8;
-      bq[ri][0] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp));
-      bq[ri][1] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp + 16));
-    }
-    auto stage = [&](int h0, auto nb_) __attribute__((always_inline)) {
-      constexpr int NB = decltype(nb_)::value;
-      const int ppr = hb * 8;                              // 16-byte pieces per key row: [K of hb heads | V of hb heads]
-      for (int i0 = tid; i0 < S * ppr; i0 += NB * 512) {
-        u32x4 v[NB];
-        int dsto[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int i = i0 + j * 512, row = i / ppr, rem = i - row * ppr;
-          const int isv = rem >= hb * 4, r2 = rem - isv * hb * 4, hl = r2 >> 2, c = r2 & 3;
-          v[j] = *reinterpret_cast<const u32x4*>(qkv_seq + (long long)row * 3 * C + (1 + isv) * C + (h0 + hl) * 32 + c * 8);
-          dsto[j] = hl * head_bytes + (isv ? S * ST_KP + row * ST_VP : row * ST_KP) + c * 16;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(smem + dsto[j]) = v[j];
-      }
-    };
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      if (ri == 0 || !all_heads) {
-        if (ri) __syncthreads();
-        const int per_thread = S * hb / 64;                // pieces per thread of this pass (S in {64, 128, 192, 256})
-        if (per_thread % 16 == 0) stage(ri * 4, std::integral_constant<int, 16>());
-        else if (per_thread % 12 == 0) stage(ri * 4, std::integral_constant<int, 12>());
-        else stage(ri * 4, std::integral_constant<int, 4>());
-        __syncthreads();
-      }
-      const int hl = (all_heads ? ri * 4 : 0) + hs;
-      const lds_char* Ks = smem + hl * head_bytes;
-      const lds_char* Vs = Ks + S * ST_KP;
-      const lds_char* kfrag = Ks + ql * ST_KP + hh * 16;
-      const lds_char* vfrag = Vs + (4 * hh + (t16 >> 2)) * ST_VP + ((g4 & 1) * 16 + (t16 & 3) * 4) * 2;
-      f32x16 o;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[r] = 0.f;
-      float m = -INFINITY, lsum = 0.f;
-      for (int kb = 0; kb < nkb; ++kb) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const u32x4 a = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(kfrag + kb * 32 * ST_KP + ks * 32);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), bq[ri][ks], s, 0, 0, 0);
-        }
-        // accumulator r of this lane is key kb * 32 + 8 (r / 4) + 4 hh + r % 4 (query ql): pad keys leave the softmax.
-        // (key 0 is real, so every block kb < nkb holds a finite score for every query)
-        float bmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r >> 2) * 8 + hh * 4 + (r & 3);
-          s[r] = key < L ? s[r] * sc2 : -INFINITY;
-          bmax = fmaxf(bmax, s[r]);
-        }
-        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
-        const float m_new = fmaxf(m, bmax);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
-          psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        if (__builtin_amdgcn_ballot_w64(m_new > m) != 0) {
-          const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-          lsum = lsum * alpha + psum;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        } else {
-          lsum += psum;
-        }
-        m = m_new;
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm) {
-          const u32x4 pb = {st_pack2(s[8 * mm + 0], s[8 * mm + 1]), st_pack2(s[8 * mm + 2], s[8 * mm + 3]),
-                            st_pack2(s[8 * mm + 4], s[8 * mm + 5]), st_pack2(s[8 * mm + 6], s[8 * mm + 7])};
-          const lds_char* vp = vfrag + (kb * 32 + 16 * mm) * ST_VP;
-          const st_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp));
-          const st_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp + 8 * ST_VP));
-          const st_s16x8 av = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, pb), o, 0, 0, 0);
-        }
-      }
-      const float inv = 1.f / lsum;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {       // d = 8 j + 4 hh + (0..3)
-        opack[ri][2 * j] = st_pack2(o[4 * j] * inv, o[4 * j + 1] * inv);
-        opack[ri][2 * j + 1] = st_pack2(o[4 * j + 2] * inv, o[4 * j + 3] * inv);
-      }
-    }
-    __syncthreads();                      // the staging region becomes operand buffers + rings
-  }
+  st_self_attention<C, TT, true, false>(opack, (const bf16_t*)p.qkv, b, lrow0, S, L, p.attn_scale, nullptr, smem, tid, lane, w);
 
   // the layer input (residual of the first epilogue): fetched and RETIRED before any weight DMA is issued
   uint2 rsd[NSL][TT];
-  {
-    const bf16_t* xr = (const bf16_t*)p.x + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s)
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt)
-        rsd[s][tt] = *reinterpret_cast<const uint2*>(xr + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  st_load_residual<C, TT, NSL, true>(rsd, (const bf16_t*)p.x + row0 * C, w, l15, lg);
   // ================================ weight stream + ring of this wave ================================
   StRing<D> rg;
-  rg.rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.wstream_b + (long long)w * ub * ST_UNIT), 0,
-                                               ub * ST_UNIT, 0x00020000);
-  rg.rs_img = rg.rs_sh;
-  rg.g_iss = 0; rg.n1 = ub; rg.n_img = 0; rg.total = ub; rg.pos_iss = 0; rg.pos_con = 0;
-  rg.ring = smem + G::RING_OFF + w * D * ST_UNIT;
-  rg.voff = lane * 16;
-#pragma unroll
-  for (int i = 0; i < D; ++i) rg.issue_one();
-  {
-    const int hs = w >> 1, qh = w & 1;
-    const int ql = lane & 31, hh = lane >> 5;
-    // attention output -> operand buffer: row qh * 32 + ql, channels h * 32 + 8 j + 4 hh .. + 4
-    const int r = qh * 32 + ql;
-#pragma unroll
-    for (int rd = 0; rd < HEADS / 4; ++rd) {
-      const int h = rd * 4 + hs;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = h * 4 + j;
-        const int phys = (c & ~15) | ((c ^ r) & 15);
-        *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + hh * 8) =
-            u32x2{opack[rd][2 * j], opack[rd][2 * j + 1]};
-      }
-    }
-  }
+  st_ring_init<D>(rg, p.wstream_b, ub, smem + G::RING_OFF, lane, w);
+  st_attn_out_to_y<C, TT, false>(opack, Y, nullptr, row0, w, lane);
   ST_BARRIER();                           // attention output complete in Y
 
   int yaddr[4], gaddr[4], woff[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int sw = (((4 * j + lg) ^ l15) & 15) * 16;
-    yaddr[j] = l15 * PITCH + sw;
-    gaddr[j] = l15 * 256 + sw;
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+  st_frag_addrs<PITCH>(l15, lg, yaddr, gaddr, woff);
   float sx[TT], sxx[TT], mean[TT], rstd[TT];
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) sx[tt] = sxx[tt] = mean[tt] = rstd[tt] = 0.f;
@@ -340,35 +166,10 @@ __global__ __launch_bounds__(512) void rollout_tail_kernel(SdmiRolloutLayerArgs 
   zero_acc();
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-#pragma unroll
-  for (int s = 0; s < NSL; ++s) {
-    const f32x4 bi = ev0[s];
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) {
-      const uint2 t2 = rsd[s][tt];
-      res[s][tt][0] = acc[s][tt][0] + bi[0] + __uint_as_float(t2.x << 16);
-      res[s][tt][1] = acc[s][tt][1] + bi[1] + __uint_as_float(t2.x & 0xffff0000u);
-      res[s][tt][2] = acc[s][tt][2] + bi[2] + __uint_as_float(t2.y << 16);
-      res[s][tt][3] = acc[s][tt][3] + bi[3] + __uint_as_float(t2.y & 0xffff0000u);
-    }
-  }
+  st_add_bias_residual<TT, NSL>(res, acc, ev0, rsd);
   ST_BARRIER();                           // every wave is done reading the attention output
-  // bf16 copy of the residual stream = the feed-forward's operand.  A pad row's input may be anything (inf, NaN): its
-  // copy is zero, so the LayerNorm statistics and the hidden chunk of that row stay finite.
-#pragma unroll
-  for (int s = 0; s < NSL; ++s) {
-    const int c = ((w * NSL + s) * 16 + 4 * lg) >> 3;
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) {
-      const int r = tt * 16 + l15;
-      const bool real = lrow0 + r < L;
-      const int phys = (c & ~15) | ((c ^ r) & 15);
-      uint2 o;
-      o.x = real ? st_pack2(res[s][tt][0], res[s][tt][1]) : 0u;
-      o.y = real ? st_pack2(res[s][tt][2], res[s][tt][3]) : 0u;
-      *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + (lg & 1) * 8) = u32x2{o.x, o.y};
-    }
-  }
+  // bf16 copy of the residual stream = the feed-forward's operand (pad rows: zeros)
+  st_rows_to_y<C, TT, NSL, false, true>(res, Y, nullptr, w, l15, lg, lrow0, L);
   ST_BARRIER();
 
   // ---- feed-forward: per hidden chunk of 128, h = relu(LN-fold(x1) W1'^T + b1') -> LDS -> acc += h W2[:, chunk]^T.

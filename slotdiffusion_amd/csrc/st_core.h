@@ -1,6 +1,18 @@
-// Shared core of the fused SpatialTransformer kernels (st_fused.hip: bf16 inference; st_train.hip: the training
-// forward / backward twins): geometry, the per-wave weight ring over LDS-DMA, one K tile of the weights-as-A GEMM
-// and the hand-off barrier.  See st_fused.hip for the layout description.
+// Tile toolkit of the fused token-row blocks -- st_fused.hip (SpatialTransformer block, bf16 inference), st_train.hip (its
+// training forward / backward twins), rollout_layer.hip (SlotFormer rollout layer): a workgroup owns 64 / 32 token rows,
+// eight symmetric waves, per-wave weight rings over LDS-DMA.  See st_fused.hip for the layout description.  One copy of
+//   geometry (StGeom), the ring (StRing, st_ring_setup / _prime / _init), the lane constants (st_frag_addrs),
+//   one K tile of the weights-as-A GEMM (st_gemm_step) with the LayerNorm-fold statistics (st_ln_stats), the hand-off
+//   barrier (ST_BARRIER) and the counted wait (ST_WAIT_UNITS),
+//   the row copies into the swizzled operand buffer (st_rows_to_y, st_load_rows_to_y) and out (st_store_rows),
+//   the residual prefetch and its epilogue (st_load_residual, st_add_bias_residual),
+//   the self-attention stage of the phase-B kernels (st_self_attention, st_attn_out_to_y).
+// Everything is __forceinline__ template code selected by compile-time parameters only, and the header is compiled per
+// translation unit: each file keeps its own code generation (csrc/build.py: -fno-slp-vectorize on two of the three).
+// What differs in substance stays with its kernel: the feed-forward chunk loops, the folded / explicit cross-attention,
+// the GroupNorm prologues.  st_fused.hip's phase A (st_block_a_kernel) keeps its own copy of the set-up, the proj_in
+// epilogue and the q | k | v passes: that file is built WITH the SLP vectoriser, and the instruction schedule the shared
+// forms gave its q | k | v epilogue hit the packed-fp32 hazard of st_train.hip's build note.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -202,6 +214,324 @@ __device__ __forceinline__ void st_ln_stats(float (&sx)[TT], float (&sxx)[TT], f
     mean[tt] = a * inv_k;
     rstd[tt] = rsqrtf(fmaxf(b * inv_k - mean[tt] * mean[tt], 0.f) + eps);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ring set-up, lane constants
+// ---------------------------------------------------------------------------------------------------------
+// One stream of `units` units per wave, nothing in flight yet: a kernel with a per-image stream or a workgroup that
+// skips part of the stream adjusts rs_img / n1 / n_img / total / jump_at / jump before st_ring_prime.
+template <int D>
+__device__ __forceinline__ void st_ring_setup(StRing<D>& rg, const void* stream, int units, lds_char* ring, int lane, int w) {
+  rg.rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)stream + (long long)w * units * ST_UNIT), 0,
+                                               units * ST_UNIT, 0x00020000);
+  rg.rs_img = rg.rs_sh;
+  rg.g_iss = 0; rg.n1 = units; rg.n_img = 0; rg.total = units; rg.pos_iss = 0; rg.pos_con = 0;
+  rg.ring = ring + w * D * ST_UNIT;
+  rg.voff = lane * 16;
+}
+template <int D>
+__device__ __forceinline__ void st_ring_prime(StRing<D>& rg) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) rg.issue_one();
+}
+template <int D>
+__device__ __forceinline__ void st_ring_init(StRing<D>& rg, const void* stream, int units, lds_char* ring, int lane, int w) {
+  st_ring_setup<D>(rg, stream, units, ring, lane, w);
+  st_ring_prime<D>(rg);
+}
+
+// Lane constants of the GEMM core: fragment offsets into the operand buffer Y (row pitch PITCH), into a 256-byte-pitch
+// chunk buffer, and into a weight unit.
+template <int PITCH>
+__device__ __forceinline__ void st_frag_addrs(int l15, int lg, int (&yaddr)[4], int (&gaddr)[4], int (&woff)[2]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int sw = (((4 * j + lg) ^ l15) & 15) * 16;
+    yaddr[j] = l15 * PITCH + sw;
+    gaddr[j] = l15 * 256 + sw;
+  }
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+}
+template <int PITCH>
+__device__ __forceinline__ void st_frag_addrs(int l15, int lg, int (&yaddr)[4], int (&woff)[2]) {
+  int gaddr[4];
+  st_frag_addrs<PITCH>(l15, lg, yaddr, gaddr, woff);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// rows <-> operand buffer Y (XOR-swizzled 16-byte chunks: chunk c of row r lies at (c & ~15) | ((c ^ r) & 15))
+// ---------------------------------------------------------------------------------------------------------
+// fp32 rows held across the workgroup (lane: row 16 tt + l15, columns (w NSL + s) 16 + 4 lg + j) -> bf16 in Y (+ optional
+// global copy).  MASKED (rollout layer): rows lrow0 + r >= L are pad rows.  A pad row's values may be anything (inf, NaN):
+// its copy is zero, so the LayerNorm statistics and the hidden chunk of that row stay finite.
+template <int C, int TT, int NSL, bool GLOBAL, bool MASKED = false>
+__device__ __forceinline__ void st_rows_to_y(const f32x4 (&x)[NSL][TT], lds_char* Y, bf16_t* gout, int w, int l15, int lg,
+                                             int lrow0 = 0, int L = 0) {
+  constexpr int PITCH = C * 2;
+#pragma unroll
+  for (int s = 0; s < NSL; ++s) {
+    const int n0 = (w * NSL + s) * 16 + 4 * lg;
+    const int c = n0 >> 3;
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const int r = tt * 16 + l15;
+      const int phys = (c & ~15) | ((c ^ r) & 15);
+      uint2 o;
+      if constexpr (MASKED) {
+        const bool real = lrow0 + r < L;
+        o.x = real ? st_pack2(x[s][tt][0], x[s][tt][1]) : 0u;
+        o.y = real ? st_pack2(x[s][tt][2], x[s][tt][3]) : 0u;
+      } else {
+        o.x = st_pack2(x[s][tt][0], x[s][tt][1]);
+        o.y = st_pack2(x[s][tt][2], x[s][tt][3]);
+      }
+      *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + (lg & 1) * 8) = u32x2{o.x, o.y};
+      if constexpr (GLOBAL) *reinterpret_cast<uint2*>(gout + (long long)r * C + n0) = o;
+    }
+  }
+}
+
+template <int C, int TT, int NSL>
+__device__ __forceinline__ void st_store_rows(const f32x4 (&x)[NSL][TT], bf16_t* gout, int ld, int w, int l15, int lg) {
+#pragma unroll
+  for (int s = 0; s < NSL; ++s) {
+    const int n0 = (w * NSL + s) * 16 + 4 * lg;
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      uint2 o;
+      o.x = st_pack2(x[s][tt][0], x[s][tt][1]);
+      o.y = st_pack2(x[s][tt][2], x[s][tt][3]);
+      *reinterpret_cast<uint2*>(gout + (long long)(tt * 16 + l15) * ld + n0) = o;
+    }
+  }
+}
+
+// ROWS x C bf16 rows from global memory (row stride ld) into Y: all 512 threads, 16-byte vectors, the loads of all
+// passes in flight before the first LDS store
+template <int C, int ROWS>
+__device__ __forceinline__ void st_load_rows_to_y(const bf16_t* src, int ld, lds_char* Y, int tid) {
+  constexpr int VPR = C / 8, PITCH = 2 * C;     // vectors per row
+  static_assert((ROWS * VPR) % 512 == 0, "whole passes");
+  u32x4 v[ROWS * VPR / 512];
+#pragma unroll
+  for (int it = 0; it < ROWS * VPR / 512; ++it) {
+    const int i = tid + it * 512, r = i / VPR, vc = i - r * VPR;
+    v[it] = *reinterpret_cast<const u32x4*>(src + (long long)r * ld + vc * 8);
+  }
+#pragma unroll
+  for (int it = 0; it < ROWS * VPR / 512; ++it) {
+    const int i = tid + it * 512, r = i / VPR, vc = i - r * VPR;
+    const int phys = (vc & ~15) | ((vc ^ r) & 15);
+    *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(Y + r * PITCH + phys * 16) = v[it];
+  }
+}
+
+// bf16 residual of an epilogue (this lane's columns of the workgroup's rows at `rows`).  An ordinary vector load issued
+// behind weight DMAs makes its consumer wait for every DMA in front of it (vmcnt retires in order): the residual is
+// fetched where no DMA is in flight -- WAIT: and RETIRED before the caller issues the first one.
+template <int C, int TT, int NSL, bool WAIT>
+__device__ __forceinline__ void st_load_residual(uint2 (&rsd)[NSL][TT], const bf16_t* rows, int w, int l15, int lg) {
+#pragma unroll
+  for (int s = 0; s < NSL; ++s)
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt)
+      rsd[s][tt] = *reinterpret_cast<const uint2*>(rows + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
+  if constexpr (WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// out = acc + bias + residual (fp32; out may be acc)
+template <int TT, int NSL>
+__device__ __forceinline__ void st_add_bias_residual(f32x4 (&out)[NSL][TT], const f32x4 (&acc)[NSL][TT],
+                                                     const f32x4 (&bias)[NSL], const uint2 (&rsd)[NSL][TT]) {
+#pragma unroll
+  for (int s = 0; s < NSL; ++s) {
+    const f32x4 bi = bias[s];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const uint2 t2 = rsd[s][tt];
+      out[s][tt][0] = acc[s][tt][0] + bi[0] + __uint_as_float(t2.x << 16);
+      out[s][tt][1] = acc[s][tt][1] + bi[1] + __uint_as_float(t2.x & 0xffff0000u);
+      out[s][tt][2] = acc[s][tt][2] + bi[2] + __uint_as_float(t2.y << 16);
+      out[s][tt][3] = acc[s][tt][3] + bi[3] + __uint_as_float(t2.y & 0xffff0000u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// self-attention stage of a phase-B kernel: 16 TT queries x HEADS heads over the S keys of the image / sequence
+// ---------------------------------------------------------------------------------------------------------
+struct StNoHook {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+
+// attention.hip's transposed matrix-core formulation (v_mfma_f32_32x32x16_bf16, V read through ds_read_tr16_b64): a wave
+// owns 32 queries of one head, four heads per round.  64 rows: two 32-query halves x four heads per round; 32 rows:
+// waves 0-3 take the four heads, waves 4-7 only stage and keep the barriers.  qkv [.][S][3C] of image / sequence `b`,
+// queries lrow0 .. lrow0 + 16 TT of it; the whole dynamic LDS is the K / V staging region, and the trailing barrier
+// hands it back (it becomes operand buffers + rings).  -> opack[round][8]: this lane's bf16 output of query row
+// qh * 32 + ql, channels h * 32 + 8 j + 4 hh .. + 4 (st_attn_out_to_y writes them out).
+// MASKED: only keys < L are real, the others leave every softmax (key 0 is real, so every 32-key block kb < nkb holds a
+// finite score for every query).  LSE: the log-sum-exp of every (head, query) -> lse1 [.][HEADS][S] (training).
+// hook(0) runs behind the first staging pass, hook(1) in front of the trailing barrier (timeline stamps of an
+// experiment build; nothing by default).
+template <int C, int TT, bool MASKED, bool LSE, class Hook = StNoHook>
+__device__ __forceinline__ void st_self_attention(unsigned (&opack)[C / 128][8], const bf16_t* qkv, int b, int lrow0, int S,
+                                                  int L, float attn_scale, float* lse1, lds_char* smem, int tid, int lane,
+                                                  int w, Hook hook = Hook()) {
+  constexpr int HEADS = C / 32;
+  const long long row0 = (long long)b * S + lrow0;
+  const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
+  const bool att_active = TT == 4 || w < 4;
+  const int ql = lane & 31, hh = lane >> 5;
+  const bf16_t* qkv_img = qkv + (long long)b * S * 3 * C;
+  const int head_bytes = S * (ST_KP + ST_VP);
+  const float sc2 = attn_scale * 1.4426950408889634f;
+  const int g4 = lane >> 4, t16 = lane & 15;
+  // K / V of `hb` heads are staged at a time: all of them when they fit (S = 64: one staging pass for the block),
+  // four otherwise; the loads of a pass are in flight together (a load per iteration behind its own wait cost a
+  // memory latency each: 27 of st_block_b_kernel's 72 us at S = 256).
+  const bool all_heads = HEADS * head_bytes <= 160 * 1024;
+  const int hb = all_heads ? HEADS : 4;
+  int nkb;                                                 // 32-key blocks that hold a real key
+  if constexpr (MASKED) nkb = (L + 31) >> 5;
+  else nkb = S / 32;
+  bf16x8 bq[HEADS / 4][2];
+#pragma unroll
+  for (int ri = 0; ri < HEADS / 4; ++ri) {
+    const bf16_t* qp = qkv + (row0 + qh * 32 + ql) * 3 * C + (ri * 4 + hs) * 32 + hh * 8;
+    bq[ri][0] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp));
+    bq[ri][1] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp + 16));
+  }
+  auto stage = [&](int h0, auto nb_) __attribute__((always_inline)) {
+    constexpr int NB = decltype(nb_)::value;
+    const int ppr = hb * 8;                              // 16-byte pieces per key row: [K of hb heads | V of hb heads]
+    for (int i0 = tid; i0 < S * ppr; i0 += NB * 512) {
+      u32x4 v[NB];
+      int dsto[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int i = i0 + j * 512, row = i / ppr, rem = i - row * ppr;
+        const int isv = rem >= hb * 4, r2 = rem - isv * hb * 4, hl = r2 >> 2, c = r2 & 3;
+        v[j] = *reinterpret_cast<const u32x4*>(qkv_img + (long long)row * 3 * C + (1 + isv) * C + (h0 + hl) * 32 + c * 8);
+        dsto[j] = hl * head_bytes + (isv ? S * ST_KP + row * ST_VP : row * ST_KP) + c * 16;
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(smem + dsto[j]) = v[j];
+    }
+  };
+#pragma unroll
+  for (int ri = 0; ri < HEADS / 4; ++ri) {
+    if (ri == 0 || !all_heads) {
+      if (ri) __syncthreads();
+      const int per_thread = S * hb / 64;                // pieces per thread of this pass (S in {64, 128, 192, 256})
+      if (per_thread % 16 == 0) stage(ri * 4, std::integral_constant<int, 16>());
+      else if (per_thread % 12 == 0) stage(ri * 4, std::integral_constant<int, 12>());
+      else stage(ri * 4, std::integral_constant<int, 4>());
+      __syncthreads();
+      if (ri == 0) hook(0);
+    }
+    const int hl = (all_heads ? ri * 4 : 0) + hs;
+    const lds_char* Ks = smem + hl * head_bytes;
+    const lds_char* Vs = Ks + S * ST_KP;
+    const lds_char* kfrag = Ks + ql * ST_KP + hh * 16;
+    const lds_char* vfrag = Vs + (4 * hh + (t16 >> 2)) * ST_VP + ((g4 & 1) * 16 + (t16 & 3) * 4) * 2;
+    if (!att_active) continue;
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    float m = -INFINITY, lsum = 0.f;
+    for (int kb = 0; kb < nkb; ++kb) {
+      f32x16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const u32x4 a = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(kfrag + kb * 32 * ST_KP + ks * 32);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), bq[ri][ks], s, 0, 0, 0);
+      }
+      float bmax = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if constexpr (MASKED) {   // accumulator r of this lane is key kb * 32 + 8 (r / 4) + 4 hh + r % 4 (query ql)
+          const int key = kb * 32 + (r >> 2) * 8 + hh * 4 + (r & 3);
+          s[r] = key < L ? s[r] * sc2 : -INFINITY;
+        } else {
+          s[r] *= sc2;
+        }
+        bmax = fmaxf(bmax, s[r]);
+      }
+      bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
+      const float m_new = fmaxf(m, bmax);
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
+        psum += s[r];
+      }
+      psum += __shfl_xor(psum, 32, 64);
+      if (__builtin_amdgcn_ballot_w64(m_new > m) != 0) {
+        const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+        lsum = lsum * alpha + psum;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[r] *= alpha;
+      } else {
+        lsum += psum;
+      }
+      m = m_new;
+#pragma unroll
+      for (int mm = 0; mm < 2; ++mm) {
+        const u32x4 pb = {st_pack2(s[8 * mm + 0], s[8 * mm + 1]), st_pack2(s[8 * mm + 2], s[8 * mm + 3]),
+                          st_pack2(s[8 * mm + 4], s[8 * mm + 5]), st_pack2(s[8 * mm + 6], s[8 * mm + 7])};
+        const lds_char* vp = vfrag + (kb * 32 + 16 * mm) * ST_VP;
+        const st_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp));
+        const st_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp + 8 * ST_VP));
+        const st_s16x8 av = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, pb), o, 0, 0, 0);
+      }
+    }
+    const float inv = 1.f / lsum;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {       // d = 8 j + 4 hh + (0..3)
+      opack[ri][2 * j] = st_pack2(o[4 * j] * inv, o[4 * j + 1] * inv);
+      opack[ri][2 * j + 1] = st_pack2(o[4 * j + 2] * inv, o[4 * j + 3] * inv);
+    }
+    if constexpr (LSE) {
+      if (hh == 0)
+        lse1[((long long)b * HEADS + (ri * 4 + hs)) * S + lrow0 + qh * 32 + ql] = m * 0.6931471805599453f + __logf(lsum);
+    }
+  }
+  hook(1);
+  __syncthreads();                      // the staging region becomes operand buffers + rings
+}
+
+// attention output -> operand buffer Y: row qh * 32 + ql, channels h * 32 + 8 j + 4 hh .. + 4.  GLOBAL: also the bf16
+// copy the training pass stores (gout: the tensor, row0: this workgroup's first row in it).
+template <int C, int TT, bool GLOBAL>
+__device__ __forceinline__ void st_attn_out_to_y(const unsigned (&opack)[C / 128][8], lds_char* Y, bf16_t* gout,
+                                                 long long row0, int w, int lane) {
+  constexpr int HEADS = C / 32, PITCH = C * 2;
+  const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
+  const int ql = lane & 31, hh = lane >> 5;
+  const int r = qh * 32 + ql;
+  bf16_t* grow = nullptr;
+  if constexpr (GLOBAL) grow = gout + (row0 + r) * C;
+  if (TT == 4 || w < 4)
+#pragma unroll
+    for (int rd = 0; rd < HEADS / 4; ++rd) {
+      const int h = rd * 4 + hs;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = h * 4 + j;
+        const int phys = (c & ~15) | ((c ^ r) & 15);
+        uint2 v;
+        v.x = opack[rd][2 * j];
+        v.y = opack[rd][2 * j + 1];
+        *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + hh * 8) = u32x2{v.x, v.y};
+        if constexpr (GLOBAL) *reinterpret_cast<uint2*>(grow + h * 32 + 8 * j + 4 * hh) = v;
+      }
+    }
 }
 
 }  // namespace

@@ -24,7 +24,7 @@
 // rows, and streams exactly the weight rows it multiplies through a PRIVATE ring of 2 KB units
 // (`buffer_load_dwordx4 ... lds`, counted `s_waitcnt vmcnt`): no barrier orders weight traffic -- the waves run
 // free inside a GEMM phase --, barriers exist only where an LDS activation buffer changes hands (~2 per phase).  The weights are pre-packed
-// on the host (kern.WeightBank.st_stream_*) into per-wave streams of units in consumption order, each unit
+// on the host (kern.WeightBank.st_fused_weights) into per-wave streams of units in consumption order, each unit
 // the exact XOR-swizzled LDS image of 16 weight rows x 64 k, so the fetch side is `base + g * 2048`.
 #include "st_core.h"
 
@@ -271,189 +271,36 @@ __global__ __launch_bounds__(512, 2) void st_block_b_kernel(SdmiStBlockArgs p) {
   ST_STAMP(0);
 
   // =========================== self-attention: 64 queries x HEADS heads over S keys ===========================
-  // (attention.hip's transposed matrix-core formulation: a wave owns 32 queries of one head; four heads per round)
   unsigned opack[HEADS / 4][8];
-  {
-    // 64 rows: two 32-query halves x four heads per round; 32 rows: waves 0-3 take the four heads, waves 4-7 only
-    // stage and keep the barriers
-    const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
-    const bool att_active = TT == 4 || w < 4;
-    const int ql = lane & 31, hh = lane >> 5;
-    const bf16_t* qkv_img = (const bf16_t*)p.qkv + (long long)b * S * 3 * C;
-    const int head_bytes = S * (ST_KP + ST_VP);
-    const float sc2 = p.attn_scale * 1.4426950408889634f;
-    const int g4 = lane >> 4, t16 = lane & 15;
-    // K / V of `hb` heads are staged at a time: all of them when they fit (S = 64: one staging pass for the block),
-    // four otherwise; the loads of a pass are in flight together (a load per iteration behind its own wait cost a
-    // memory latency each: 27 of the kernel's 72 us at S = 256).
-    const bool all_heads = HEADS * head_bytes <= 160 * 1024;
-    const int hb = all_heads ? HEADS : 4;
-    bf16x8 bq[HEADS / 4][2];
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      const bf16_t* qp = (const bf16_t*)p.qkv + (row0 + qh * 32 + ql) * 3 * C + (ri * 4 + hs) * 32 + hh * 8;
-      bq[ri][0] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp));
-      bq[ri][1] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp + 16));
-    }
-    auto stage = [&](int h0, auto nb_) __attribute__((always_inline)) {
-      constexpr int NB = decltype(nb_)::value;
-      const int ppr = hb * 8;                              // 16-byte pieces per key row: [K of hb heads | V of hb heads]
-      for (int i0 = tid; i0 < S * ppr; i0 += NB * 512) {
-        u32x4 v[NB];
-        int dsto[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int i = i0 + j * 512, row = i / ppr, rem = i - row * ppr;
-          const int isv = rem >= hb * 4, r2 = rem - isv * hb * 4, hl = r2 >> 2, c = r2 & 3;
-          v[j] = *reinterpret_cast<const u32x4*>(qkv_img + (long long)row * 3 * C + (1 + isv) * C + (h0 + hl) * 32 + c * 8);
-          dsto[j] = hl * head_bytes + (isv ? S * ST_KP + row * ST_VP : row * ST_KP) + c * 16;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(smem + dsto[j]) = v[j];
-      }
-    };
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      if (ri == 0 || !all_heads) {
-        if (ri) __syncthreads();
-        const int per_thread = S * hb / 64;                // pieces per thread of this pass
-        if (per_thread % 16 == 0) stage(ri * 4, std::integral_constant<int, 16>());
-        else if (per_thread % 12 == 0) stage(ri * 4, std::integral_constant<int, 12>());
-        else stage(ri * 4, std::integral_constant<int, 4>());
-        __syncthreads();
-        if (ri == 0) ST_STAMP(8);
-      }
-      const int hl = (all_heads ? ri * 4 : 0) + hs;
-      const lds_char* Ks = smem + hl * head_bytes;
-      const lds_char* Vs = Ks + S * ST_KP;
-      const lds_char* kfrag = Ks + ql * ST_KP + hh * 16;
-      const lds_char* vfrag = Vs + (4 * hh + (t16 >> 2)) * ST_VP + ((g4 & 1) * 16 + (t16 & 3) * 4) * 2;
-      const int rd = ri;
-      if (!att_active) continue;
-      f32x16 o;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[r] = 0.f;
-      float m = -INFINITY, lsum = 0.f;
-      for (int kb = 0; kb < S / 32; ++kb) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const u32x4 a = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(kfrag + kb * 32 * ST_KP + ks * 32);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), bq[ri][ks], s, 0, 0, 0);
-        }
-        float bmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] *= sc2;
-          bmax = fmaxf(bmax, s[r]);
-        }
-        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
-        const float m_new = fmaxf(m, bmax);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
-          psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        if (__builtin_amdgcn_ballot_w64(m_new > m) != 0) {
-          const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-          lsum = lsum * alpha + psum;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        } else {
-          lsum += psum;
-        }
-        m = m_new;
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm) {
-          const u32x4 pb = {st_pack2(s[8 * mm + 0], s[8 * mm + 1]), st_pack2(s[8 * mm + 2], s[8 * mm + 3]),
-                            st_pack2(s[8 * mm + 4], s[8 * mm + 5]), st_pack2(s[8 * mm + 6], s[8 * mm + 7])};
-          const lds_char* vp = vfrag + (kb * 32 + 16 * mm) * ST_VP;
-          const st_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp));
-          const st_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp + 8 * ST_VP));
-          const st_s16x8 av = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, pb), o, 0, 0, 0);
-        }
-      }
-      const float inv = 1.f / lsum;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {       // d = 8 j + 4 hh + (0..3)
-        opack[rd][2 * j] = st_pack2(o[4 * j] * inv, o[4 * j + 1] * inv);
-        opack[rd][2 * j + 1] = st_pack2(o[4 * j + 2] * inv, o[4 * j + 3] * inv);
-      }
-    }
-    ST_STAMP(9);
-    __syncthreads();                      // the staging region becomes operand buffers + rings
-    ST_STAMP(10);
-  }
+  st_self_attention<C, TT, false, false>(opack, (const bf16_t*)p.qkv, b, rb * ROWS, S, S, p.attn_scale, nullptr, smem, tid, lane, w,
+                                         [&](int i) __attribute__((always_inline)) { ST_STAMP(8 + i); });
+  ST_STAMP(10);
 
-  // the token residual of the first epilogue: fetched and RETIRED before any weight DMA is issued (st_vec4's note)
+  // the token residual of the first epilogue: fetched and RETIRED before any weight DMA is issued
   uint2 rsd[NSL][TT];
-  {
-    const bf16_t* tok = (const bf16_t*)p.tok + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s)
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt)
-        rsd[s][tt] = *reinterpret_cast<const uint2*>(tok + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  st_load_residual<C, TT, NSL, true>(rsd, (const bf16_t*)p.tok + row0 * C, w, l15, lg);
   ST_STAMP(11);
   // the second-dispatched half of the workgroup loses issue arbitration to the first on every SIMD and arrives last
   // at each hand-off barrier (the FF loop's wave 0 spent 22 % of its time waiting there): static priority for it
   if (w >= 4) __builtin_amdgcn_s_setprio(1);
   // ================================ weight stream + ring of this wave ================================
   StRing<D> rg;
-  rg.rs_sh = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const char*)p.wstream_b + (long long)w * (G::UB1 + G::UB2) * ST_UNIT), 0, (G::UB1 + G::UB2) * ST_UNIT, 0x00020000);
+  st_ring_setup<D>(rg, p.wstream_b, G::UB1 + G::UB2, smem + G::RING_OFF, lane, w);
   rg.rs_img = __builtin_amdgcn_make_buffer_rsrc(
       (void*)((const char*)p.wstream_img + ((long long)b * 8 + w) * G::UIMG * ST_UNIT), 0, G::UIMG * ST_UNIT, 0x00020000);
-  rg.g_iss = 0; rg.n1 = G::UB1; rg.n_img = G::UIMG; rg.total = G::UB1 + G::UIMG + G::UB2;
+  rg.n1 = G::UB1; rg.n_img = G::UIMG; rg.total = G::UB1 + G::UIMG + G::UB2;
   constexpr int UCH = KT * 2 + 2 * NSL;                 // units of one hidden chunk
   if (ffs == 2) {                                        // this workgroup's half of the hidden chunks
     rg.total -= (G::NHC / 2) * UCH;
     if (half) { rg.jump_at = G::UB1 + KT * NSL; rg.jump = (G::NHC / 2) * UCH; }
   }
-  rg.pos_iss = 0; rg.pos_con = 0;
-  rg.ring = smem + G::RING_OFF + w * D * ST_UNIT;
-  rg.voff = lane * 16;
-#pragma unroll
-  for (int i = 0; i < D; ++i) rg.issue_one();
-  {
-    const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
-    const int ql = lane & 31, hh = lane >> 5;
-    // attention output -> operand buffer: row qh * 32 + ql, channels h * 32 + 8 j + 4 hh .. + 4
-    const int r = qh * 32 + ql;
-    if (TT == 4 || w < 4)
-#pragma unroll
-    for (int rd = 0; rd < HEADS / 4; ++rd) {
-      const int h = rd * 4 + hs;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = h * 4 + j;
-        const int phys = (c & ~15) | ((c ^ r) & 15);
-        uint2 v;
-        v.x = opack[rd][2 * j];
-        v.y = opack[rd][2 * j + 1];
-        *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + hh * 8) = u32x2{v.x, v.y};
-      }
-    }
-  }
+  st_ring_prime<D>(rg);
+  st_attn_out_to_y<C, TT, false>(opack, Y, nullptr, row0, w, lane);
   ST_BARRIER();                           // attention output complete in Y
   ST_STAMP(1);
 
   int yaddr[4], gaddr[4], woff[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int sw = (((4 * j + lg) ^ l15) & 15) * 16;
-    yaddr[j] = l15 * PITCH + sw;
-    gaddr[j] = l15 * 256 + sw;
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+  st_frag_addrs<PITCH>(l15, lg, yaddr, gaddr, woff);
   float sx[TT], sxx[TT], mean[TT], rstd[TT];
   const float* vb = p.vec_b;              // [bo | bo2 | colsum_ff (8C) | bias_ff (8C) | bias_out]  fp32
   const float* vi = p.vec_img + (long long)b * 256;   // per image: [colsum_q (128) | bias_q (128)]
@@ -466,21 +313,6 @@ __global__ __launch_bounds__(512, 2) void st_block_b_kernel(SdmiStBlockArgs p) {
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt) acc[s][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
-  auto res_to_y = [&]() __attribute__((always_inline)) {      // bf16 copy of the residual stream = next GEMM's operand
-#pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const int c = ((w * NSL + s) * 16 + 4 * lg) >> 3;
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt) {
-        const int r = tt * 16 + l15;
-        const int phys = (c & ~15) | ((c ^ r) & 15);
-        uint2 o;
-        o.x = st_pack2(res[s][tt][0], res[s][tt][1]);
-        o.y = st_pack2(res[s][tt][2], res[s][tt][3]);
-        *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + (lg & 1) * 8) = u32x2{o.x, o.y};
-      }
-    }
-  };
 
   // (epilogue operands are fetched BEFORE the GEMM they follow -- see phase A)
   ST_STAMP(2);
@@ -491,22 +323,9 @@ __global__ __launch_bounds__(512, 2) void st_block_b_kernel(SdmiStBlockArgs p) {
   zero_acc();
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-  {
-#pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const f32x4 bi = ev0[s];
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt) {
-        const uint2 t2 = rsd[s][tt];
-        res[s][tt][0] = acc[s][tt][0] + bi[0] + __uint_as_float(t2.x << 16);
-        res[s][tt][1] = acc[s][tt][1] + bi[1] + __uint_as_float(t2.x & 0xffff0000u);
-        res[s][tt][2] = acc[s][tt][2] + bi[2] + __uint_as_float(t2.y << 16);
-        res[s][tt][3] = acc[s][tt][3] + bi[3] + __uint_as_float(t2.y & 0xffff0000u);
-      }
-    }
-  }
+  st_add_bias_residual<TT, NSL>(res, acc, ev0, rsd);
   ST_BARRIER();
-  res_to_y();
+  st_rows_to_y<C, TT, NSL, false>(res, Y, nullptr, w, l15, lg);     // bf16 copy of the residual stream = next GEMM's operand
   ST_BARRIER();
 
   ST_STAMP(3);
@@ -573,7 +392,7 @@ __global__ __launch_bounds__(512, 2) void st_block_b_kernel(SdmiStBlockArgs p) {
       for (int j = 0; j < 4; ++j) res[s][tt][j] += acc[s][tt][j] + bi[j];
   }
   ST_BARRIER();                                         // (Y readers of the score GEMM are long done; Gb readers too)
-  res_to_y();
+  st_rows_to_y<C, TT, NSL, false>(res, Y, nullptr, w, l15, lg);
   ST_BARRIER();
 
   ST_STAMP(4);
@@ -645,35 +464,11 @@ __global__ __launch_bounds__(512, 2) void st_block_b_kernel(SdmiStBlockArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
   }
-  {
-    const bf16_t* xr = (const bf16_t*)p.x + row0 * C;
 #pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      ev0[s] = st_vec4(vb + 18 * C + (w * NSL + s) * 16, lg);
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt)
-        rsd[s][tt] = *reinterpret_cast<const uint2*>(xr + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
-    }
-  }
-  {
-    bf16_t* outp = (bf16_t*)p.out + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const int n0 = (w * NSL + s) * 16 + 4 * lg;
-      const f32x4 bi = ev0[s];
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt) {
-        const long long o_ = (long long)(tt * 16 + l15) * C + n0;
-        const uint2 x2 = rsd[s][tt];
-        uint2 o;
-        o.x = st_pack2(acc[s][tt][0] + bi[0] + __uint_as_float(x2.x << 16),
-                       acc[s][tt][1] + bi[1] + __uint_as_float(x2.x & 0xffff0000u));
-        o.y = st_pack2(acc[s][tt][2] + bi[2] + __uint_as_float(x2.y << 16),
-                       acc[s][tt][3] + bi[3] + __uint_as_float(x2.y & 0xffff0000u));
-        *reinterpret_cast<uint2*>(outp + o_) = o;
-      }
-    }
-  }
+  for (int s = 0; s < NSL; ++s) ev0[s] = st_vec4(vb + 18 * C + (w * NSL + s) * 16, lg);
+  st_load_residual<C, TT, NSL, false>(rsd, (const bf16_t*)p.x + row0 * C, w, l15, lg);
+  st_add_bias_residual<TT, NSL>(acc, acc, ev0, rsd);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.out + row0 * C, C, w, l15, lg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   ST_STAMP(6);
 }

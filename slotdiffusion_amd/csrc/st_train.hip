@@ -5,7 +5,8 @@
 //
 // Same skeleton as st_fused.hip (a workgroup owns 64 / 32 token rows of one image, eight symmetric waves, each streaming
 // the weight rows it multiplies through a private ring of LDS-DMA units, weights as the MFMA A operand so that a lane
-// holds four consecutive output columns of one token row) -- but in the form a TRAINING step needs:
+// holds four consecutive output columns of one token row), built from the same pieces (st_core.h: ring, GEMM step,
+// self-attention stage, row <-> operand buffer copies) -- but in the form a TRAINING step needs:
 //   * plain weights (the weights change every step: no LayerNorm fold, no ff.net.2 / proj_out merge), re-packed into
 //     unit streams by st_pack_kernel after every optimiser step;
 //   * LayerNorm explicitly on the fp32 residual stream (row statistics exchanged between the waves through LDS): the
@@ -73,18 +74,6 @@ __device__ __forceinline__ float st_sum_row16(float v) {      // sum over the 16
   return v;
 }
 
-template <int D>
-__device__ __forceinline__ void st_ring_init(StRing<D>& rg, const void* stream, int units, lds_char* ring, int lane, int w) {
-  rg.rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)stream + (long long)w * units * ST_UNIT), 0,
-                                               units * ST_UNIT, 0x00020000);
-  rg.rs_img = rg.rs_sh;
-  rg.g_iss = 0; rg.n1 = units; rg.n_img = 0; rg.total = units; rg.pos_iss = 0; rg.pos_con = 0;
-  rg.ring = ring + w * D * ST_UNIT;
-  rg.voff = lane * 16;
-#pragma unroll
-  for (int i = 0; i < D; ++i) rg.issue_one();
-}
-
 // LayerNorm of the fp32 rows held across the workgroup (lane: row 16 tt + l15, columns (w NSL + s) 16 + 4 lg + j):
 // row sums exchanged through `red` ([wave][row] float2), then n = (x - mean) rstd gamma + beta as bf16 into the operand
 // buffer Y and to `nout`; (mean, rstd) to `stout` (wave 0).  Two workgroup barriers: the first also tells that every
@@ -135,42 +124,6 @@ __device__ __forceinline__ void st_layernorm_rows(const f32x4 (&x)[NSL][TT], con
     }
   }
   ST_BARRIER();
-}
-
-// bf16 rows held across the workgroup (fp32 values x) -> operand buffer Y (+ optional global copy)
-template <int C, int TT, int NSL, bool GLOBAL>
-__device__ __forceinline__ void st_rows_to_y(const f32x4 (&x)[NSL][TT], lds_char* Y, bf16_t* gout, int w, int l15, int lg) {
-  constexpr int PITCH = C * 2;
-#pragma unroll
-  for (int s = 0; s < NSL; ++s) {
-    const int n0 = (w * NSL + s) * 16 + 4 * lg;
-    const int c = n0 >> 3;
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) {
-      const int r = tt * 16 + l15;
-      const int phys = (c & ~15) | ((c ^ r) & 15);
-      uint2 o;
-      o.x = st_pack2(x[s][tt][0], x[s][tt][1]);
-      o.y = st_pack2(x[s][tt][2], x[s][tt][3]);
-      *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + (lg & 1) * 8) = u32x2{o.x, o.y};
-      if constexpr (GLOBAL) *reinterpret_cast<uint2*>(gout + (long long)r * C + n0) = o;
-    }
-  }
-}
-
-template <int C, int TT, int NSL>
-__device__ __forceinline__ void st_store_rows(const f32x4 (&x)[NSL][TT], bf16_t* gout, int ld, int w, int l15, int lg) {
-#pragma unroll
-  for (int s = 0; s < NSL; ++s) {
-    const int n0 = (w * NSL + s) * 16 + 4 * lg;
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) {
-      uint2 o;
-      o.x = st_pack2(x[s][tt][0], x[s][tt][1]);
-      o.y = st_pack2(x[s][tt][2], x[s][tt][3]);
-      *reinterpret_cast<uint2*>(gout + (long long)(tt * 16 + l15) * ld + n0) = o;
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -273,10 +226,7 @@ __global__ __launch_bounds__(512) void st_train_a_kernel(SdmiStTrainArgs p) {
   ST_BARRIER();
 
   int yaddr[4], woff[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) yaddr[j] = l15 * PITCH + ((((4 * j + lg) ^ l15) & 15) * 16);
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+  st_frag_addrs<PITCH>(l15, lg, yaddr, woff);
   float sx[TT], sxx[TT];
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) sx[tt] = sxx[tt] = 0.f;
@@ -340,127 +290,14 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
   const int S = p.S;
 
   // =========================== self-attention: ROWS queries x HEADS heads over S keys ===========================
-  // (st_fused.hip's phase B; additionally lse1 for the backward pass)
+  // (additionally lse1 for the backward pass)
   unsigned opack[HEADS / 4][8];
-  {
-    const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
-    const bool att_active = TT == 4 || w < 4;
-    const int ql = lane & 31, hh = lane >> 5;
-    const bf16_t* qkv_img = (const bf16_t*)p.qkv + (long long)b * S * 3 * C;
-    const int head_bytes = S * (ST_KP + ST_VP);
-    const float sc2 = p.attn_scale * 1.4426950408889634f;
-    const int g4 = lane >> 4, t16 = lane & 15;
-    const bool all_heads = HEADS * head_bytes <= 160 * 1024;
-    const int hb = all_heads ? HEADS : 4;
-    bf16x8 bq[HEADS / 4][2];
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      const bf16_t* qp = (const bf16_t*)p.qkv + (row0 + qh * 32 + ql) * 3 * C + (ri * 4 + hs) * 32 + hh * 8;
-      bq[ri][0] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp));
-      bq[ri][1] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp + 16));
-    }
-    auto stage = [&](int h0, auto nb_) __attribute__((always_inline)) {
-      constexpr int NB = decltype(nb_)::value;
-      const int ppr = hb * 8;
-      for (int i0 = tid; i0 < S * ppr; i0 += NB * 512) {
-        u32x4 v[NB];
-        int dsto[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int i = i0 + j * 512, row = i / ppr, rem = i - row * ppr;
-          const int isv = rem >= hb * 4, r2 = rem - isv * hb * 4, hl = r2 >> 2, c = r2 & 3;
-          v[j] = *reinterpret_cast<const u32x4*>(qkv_img + (long long)row * 3 * C + (1 + isv) * C + (h0 + hl) * 32 + c * 8);
-          dsto[j] = hl * head_bytes + (isv ? S * ST_KP + row * ST_VP : row * ST_KP) + c * 16;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(smem + dsto[j]) = v[j];
-      }
-    };
-#pragma unroll
-    for (int ri = 0; ri < HEADS / 4; ++ri) {
-      if (ri == 0 || !all_heads) {
-        if (ri) __syncthreads();
-        const int per_thread = S * hb / 64;
-        if (per_thread % 16 == 0) stage(ri * 4, std::integral_constant<int, 16>());
-        else if (per_thread % 12 == 0) stage(ri * 4, std::integral_constant<int, 12>());
-        else stage(ri * 4, std::integral_constant<int, 4>());
-        __syncthreads();
-      }
-      const int hl = (all_heads ? ri * 4 : 0) + hs;
-      const lds_char* Ks = smem + hl * head_bytes;
-      const lds_char* Vs = Ks + S * ST_KP;
-      const lds_char* kfrag = Ks + ql * ST_KP + hh * 16;
-      const lds_char* vfrag = Vs + (4 * hh + (t16 >> 2)) * ST_VP + ((g4 & 1) * 16 + (t16 & 3) * 4) * 2;
-      if (!att_active) continue;
-      f32x16 o;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[r] = 0.f;
-      float m = -INFINITY, lsum = 0.f;
-      for (int kb = 0; kb < S / 32; ++kb) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const u32x4 a = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(kfrag + kb * 32 * ST_KP + ks * 32);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), bq[ri][ks], s, 0, 0, 0);
-        }
-        float bmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] *= sc2;
-          bmax = fmaxf(bmax, s[r]);
-        }
-        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
-        const float m_new = fmaxf(m, bmax);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
-          psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        if (__builtin_amdgcn_ballot_w64(m_new > m) != 0) {
-          const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-          lsum = lsum * alpha + psum;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        } else {
-          lsum += psum;
-        }
-        m = m_new;
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm) {
-          const u32x4 pb = {st_pack2(s[8 * mm + 0], s[8 * mm + 1]), st_pack2(s[8 * mm + 2], s[8 * mm + 3]),
-                            st_pack2(s[8 * mm + 4], s[8 * mm + 5]), st_pack2(s[8 * mm + 6], s[8 * mm + 7])};
-          const lds_char* vp = vfrag + (kb * 32 + 16 * mm) * ST_VP;
-          const st_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp));
-          const st_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ST_LDS_V4(vp + 8 * ST_VP));
-          const st_s16x8 av = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, pb), o, 0, 0, 0);
-        }
-      }
-      const float inv = 1.f / lsum;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {       // d = 8 j + 4 hh + (0..3)
-        opack[ri][2 * j] = st_pack2(o[4 * j] * inv, o[4 * j + 1] * inv);
-        opack[ri][2 * j + 1] = st_pack2(o[4 * j + 2] * inv, o[4 * j + 3] * inv);
-      }
-      if (hh == 0)
-        p.lse1[((long long)b * HEADS + (ri * 4 + hs)) * S + rb * ROWS + qh * 32 + ql] = m * 0.6931471805599453f + __logf(lsum);
-    }
-    __syncthreads();                      // the staging region becomes operand buffers + rings
-  }
+  st_self_attention<C, TT, false, true>(opack, (const bf16_t*)p.qkv, b, rb * ROWS, S, S, p.attn_scale, p.lse1, smem, tid, lane, w);
 
   // the token residual of the first epilogue and the slot keys / values: fetched and RETIRED before any weight DMA
   uint2 rsd[NSL][TT];
+  st_load_residual<C, TT, NSL, false>(rsd, (const bf16_t*)p.tok + row0 * C, w, l15, lg);
   {
-    const bf16_t* tok = (const bf16_t*)p.tok + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s)
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt)
-        rsd[s][tt] = *reinterpret_cast<const uint2*>(tok + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
     const bf16_t* kvg = (const bf16_t*)p.kv2 + (long long)b * p.slots * p.ldkv;
     const int vpr = 2 * C / 8;                                 // 16-byte vectors per slot row
     for (int i = tid; i < p.slots * vpr; i += 512) {
@@ -473,38 +310,11 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
   if (w >= 4) __builtin_amdgcn_s_setprio(1);
   StRing<D> rg;
   st_ring_init<D>(rg, p.wstream_b, G::UB, smem + G::RING_OFF, lane, w);
-  {
-    const int hs = TT == 4 ? (w >> 1) : (w & 3), qh = TT == 4 ? (w & 1) : 0;
-    const int ql = lane & 31, hh = lane >> 5;
-    const int r = qh * 32 + ql;
-    bf16_t* a1 = (bf16_t*)p.a1 + (row0 + r) * C;
-    if (TT == 4 || w < 4)
-#pragma unroll
-      for (int rd = 0; rd < HEADS / 4; ++rd) {
-        const int h = rd * 4 + hs;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c = h * 4 + j;
-          const int phys = (c & ~15) | ((c ^ r) & 15);
-          uint2 v;
-          v.x = opack[rd][2 * j];
-          v.y = opack[rd][2 * j + 1];
-          *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(Y + r * PITCH + phys * 16 + hh * 8) = u32x2{v.x, v.y};
-          *reinterpret_cast<uint2*>(a1 + h * 32 + 8 * j + 4 * hh) = v;
-        }
-      }
-  }
+  st_attn_out_to_y<C, TT, true>(opack, Y, (bf16_t*)p.a1, row0, w, lane);
   ST_BARRIER();                           // attention output complete in Y, slot keys / values in KV
 
   int yaddr[4], gaddr[4], woff[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int sw = (((4 * j + lg) ^ l15) & 15) * 16;
-    yaddr[j] = l15 * PITCH + sw;
-    gaddr[j] = l15 * 256 + sw;
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16);
+  st_frag_addrs<PITCH>(l15, lg, yaddr, gaddr, woff);
   float sx[TT], sxx[TT];
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) sx[tt] = sxx[tt] = 0.f;
@@ -530,16 +340,7 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
   zero_acc();
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
-#pragma unroll
-  for (int s = 0; s < NSL; ++s)
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) {
-      const uint2 t2 = rsd[s][tt];
-      res[s][tt][0] = acc[s][tt][0] + ev0[s][0] + __uint_as_float(t2.x << 16);
-      res[s][tt][1] = acc[s][tt][1] + ev0[s][1] + __uint_as_float(t2.x & 0xffff0000u);
-      res[s][tt][2] = acc[s][tt][2] + ev0[s][2] + __uint_as_float(t2.y << 16);
-      res[s][tt][3] = acc[s][tt][3] + ev0[s][3] + __uint_as_float(t2.y & 0xffff0000u);
-    }
+  st_add_bias_residual<TT, NSL>(res, acc, ev0, rsd);
   st_store_rows<C, TT, NSL>(res, (bf16_t*)p.x1 + row0 * C, C, w, l15, lg);
   st_layernorm_rows<C, TT, NSL>(res, evg, evb, p.ln_eps, Y, lnred, (bf16_t*)p.n2 + row0 * C, p.st2 + row0 * 2, w, l15, lg);
 
@@ -700,30 +501,9 @@ __global__ __launch_bounds__(512) void st_train_b_kernel(SdmiStTrainArgs p) {
   for (int kt = 1; kt < KT; ++kt) st_gemm_step<D, NSL, false, 0, TT>(rg, Y, yaddr, kt, 16 * PITCH, woff, acc, sx, sxx);
   // (only dummy re-fetches are in flight now: drain them, then ordinary loads are safe)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  {
-    const bf16_t* xr = (const bf16_t*)p.x + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s)
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt)
-        rsd[s][tt] = *reinterpret_cast<const uint2*>(xr + (long long)(tt * 16 + l15) * C + (w * NSL + s) * 16 + 4 * lg);
-    bf16_t* outp = (bf16_t*)p.out + row0 * C;
-#pragma unroll
-    for (int s = 0; s < NSL; ++s) {
-      const int n0 = (w * NSL + s) * 16 + 4 * lg;
-      const f32x4 bi = ev0[s];
-#pragma unroll
-      for (int tt = 0; tt < TT; ++tt) {
-        const uint2 x2 = rsd[s][tt];
-        uint2 o;
-        o.x = st_pack2(acc[s][tt][0] + bi[0] + __uint_as_float(x2.x << 16),
-                       acc[s][tt][1] + bi[1] + __uint_as_float(x2.x & 0xffff0000u));
-        o.y = st_pack2(acc[s][tt][2] + bi[2] + __uint_as_float(x2.y << 16),
-                       acc[s][tt][3] + bi[3] + __uint_as_float(x2.y & 0xffff0000u));
-        *reinterpret_cast<uint2*>(outp + (long long)(tt * 16 + l15) * C + n0) = o;
-      }
-    }
-  }
+  st_load_residual<C, TT, NSL, false>(rsd, (const bf16_t*)p.x + row0 * C, w, l15, lg);
+  st_add_bias_residual<TT, NSL>(acc, acc, ev0, rsd);
+  st_store_rows<C, TT, NSL>(acc, (bf16_t*)p.out + row0 * C, C, w, l15, lg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -771,25 +551,6 @@ struct StTrBwdGeom {
   static constexpr int UB2 = 2 * KT * NSL;                             // to_q2^T, to_out^T
   static constexpr int UA = 4 * KT * NSL;                              // q^T, k^T, v^T, proj_in^T
 };
-
-// ROWS x C bf16 rows from global memory into the swizzled operand buffer (all 512 threads, 16-byte vectors)
-template <int C, int TT>
-__device__ __forceinline__ void st_rows_global_to_y(const bf16_t* src, int ld, lds_char* Y, int tid) {
-  constexpr int ROWS = 16 * TT, VPR = C / 8, PITCH = 2 * C;
-  static_assert((ROWS * VPR) % 512 == 0, "whole passes");
-  u32x4 v[ROWS * VPR / 512];
-#pragma unroll
-  for (int it = 0; it < ROWS * VPR / 512; ++it) {
-    const int i = tid + it * 512, r = i / VPR, vc = i - r * VPR;
-    v[it] = *reinterpret_cast<const u32x4*>(src + (long long)r * ld + vc * 8);
-  }
-#pragma unroll
-  for (int it = 0; it < ROWS * VPR / 512; ++it) {
-    const int i = tid + it * 512, r = i / VPR, vc = i - r * VPR;
-    const int phys = (vc & ~15) | ((vc ^ r) & 15);
-    *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(Y + r * PITCH + phys * 16) = v[it];
-  }
-}
 
 // LayerNorm backward on rows held across the workgroup: dn (gradient of the normalised rows, fp32) ->
 //   dx = rstd (g - mean_k g - xhat mean_k (g xhat)) + residual gradient,   g = dn gamma, xhat = (x - mean) rstd
@@ -894,12 +655,7 @@ __device__ __forceinline__ void st_ln_bwd_rows(f32x4 (&dn)[NSL][TT], const bf16_
   const int vid = st_xcd_id((int)blockIdx.x, (int)gridDim.x);                                         \
   const long long row0 = (long long)vid * GEOM::ROWS;                                                 \
   int yaddr[4], gaddr[4], woff[2];                                                                    \
-  _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                     \
-    const int sw = (((4 * j + lg) ^ l15) & 15) * 16;                                                  \
-    yaddr[j] = l15 * GEOM::PITCH + sw;                                                                \
-    gaddr[j] = l15 * 256 + sw;                                                                        \
-  }                                                                                                   \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) woff[ks] = l15 * 128 + (((4 * ks + lg) ^ ((l15 >> 1) & 7)) * 16); \
+  st_frag_addrs<GEOM::PITCH>(l15, lg, yaddr, gaddr, woff);                                            \
   float sx[TT], sxx[TT];                                                                              \
   _Pragma("unroll") for (int tt = 0; tt < TT; ++tt) sx[tt] = sxx[tt] = 0.f;                           \
   (void)gaddr
@@ -915,7 +671,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_b1_kernel(SdmiStTrainBwdArgs
   float* const red = (float*)(smem_ + G::RED1_OFF);
   StRing<D> rg;
   st_ring_init<D>(rg, p.wstream_b1, G::UB1, smem + G::RING1_OFF, lane, w);
-  st_rows_global_to_y<C, TT>((const bf16_t*)p.dout + row0 * C, C, Y, tid);
+  st_load_rows_to_y<C, G::ROWS>((const bf16_t*)p.dout + row0 * C, C, Y, tid);
   ST_BARRIER();
   f32x4 res[NSL][TT], acc[NSL][TT];
   auto zero_acc = [&]() __attribute__((always_inline)) {
@@ -1012,7 +768,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_b2_kernel(SdmiStTrainBwdArgs
   float* const red = (float*)(smem_ + G::RED2_OFF);
   StRing<D> rg;
   st_ring_init<D>(rg, p.wstream_b2, G::UB2, smem + G::RING2_OFF, lane, w);
-  st_rows_global_to_y<C, TT>((const bf16_t*)p.dq2 + row0 * C, C, Y, tid);
+  st_load_rows_to_y<C, G::ROWS>((const bf16_t*)p.dq2 + row0 * C, C, Y, tid);
   ST_BARRIER();
   f32x4 acc[NSL][TT];
 #pragma unroll
@@ -1046,7 +802,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_a_kernel(SdmiStTrainBwdArgs 
   StRing<D> rg;
   st_ring_init<D>(rg, p.wstream_a, G::UA, smem + G::RING2_OFF, lane, w);
   const bf16_t* dqkv = (const bf16_t*)p.dqkv + row0 * 3 * C;
-  st_rows_global_to_y<C, TT>(dqkv, 3 * C, Y, tid);
+  st_load_rows_to_y<C, G::ROWS>(dqkv, 3 * C, Y, tid);
   ST_BARRIER();
   f32x4 acc[NSL][TT];
 #pragma unroll
@@ -1057,7 +813,7 @@ __global__ __launch_bounds__(512) void st_train_bwd_a_kernel(SdmiStTrainBwdArgs 
   for (int pass = 0; pass < 3; ++pass) {
     if (pass) {
       ST_BARRIER();                                     // every wave is done with the previous part of dqkv
-      st_rows_global_to_y<C, TT>(dqkv + pass * C, 3 * C, Y, tid);
+      st_load_rows_to_y<C, G::ROWS>(dqkv + pass * C, 3 * C, Y, tid);
       ST_BARRIER();
     }
 #pragma unroll

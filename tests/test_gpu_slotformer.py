@@ -95,11 +95,12 @@ def test_model_fp32_matches_the_reference_fixture():
         assert len(errs) == 3 and float(rel.max()) <= 2e-2 and max(errs.values()) <= 2e-2
 
 
-@pytest.mark.parametrize('history,slots', [(15, 8), (6, 7), (8, 8), (2, 8)])
+@pytest.mark.parametrize('history,slots', [(15, 8), (6, 7), (8, 8), (2, 8), (21, 8), (25, 8)])
 def test_fused_layer_matches_per_layer_launches_and_fp32(history, slots):
-    """One layer at L = 120 (padded to 128, the shipped shape), 42 (a partly filled row tile), 64 (no padding) and 16
-    (less than one tile of keys): rel-L2 against the fp32 restatement under the fused-block bars of
-    test_gpu_st_fused.py, and no worse than the per-layer bf16 launches it replaces."""
+    """One layer at L = 120 (padded to 128, the shipped shape), 42 (a partly filled row tile), 64 (no padding), 16
+    (less than one tile of keys), 168 (Lp = 192: keys / values staged four heads at a time, twelve pieces per thread)
+    and 200 (Lp = 256: four heads at a time, sixteen pieces): rel-L2 against the fp32 restatement under the fused-block
+    bars of test_gpu_st_fused.py, and no worse than the per-layer bf16 launches it replaces."""
     from slotdiffusion_amd import engine
     m = R.gpu_model(decoder=True)
     x, L = _layer_input(history, slots)
@@ -117,7 +118,7 @@ def test_fused_layer_matches_per_layer_launches_and_fp32(history, slots):
     assert e_f < 2.0 * e_p + 2e-3
 
 
-@pytest.mark.parametrize('history,slots', [(15, 8), (6, 7)])
+@pytest.mark.parametrize('history,slots', [(15, 8), (6, 7), (25, 8)])
 def test_pad_rows_never_reach_a_real_row(history, slots):
     m = R.gpu_model(decoder=True)
     x0, L = _layer_input(history, slots, pad=0.0)
