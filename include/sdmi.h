@@ -1134,6 +1134,36 @@ typedef struct {
 } SdmiPredStepArgs;
 int sdmi_pred_step(const SdmiPredStepArgs* a, void* stream);
 
+/* The transformer slot transition of one frame as ONE launch (bf16 operands, inference; video_based/models/
+ * predictor.py:20-44: nn.TransformerEncoder, norm_first, ReLU feed-forward, no dropout at inference).  Per layer l:
+ *   x += W_o MHA(LN1(x)) + b_o        MHA: q | k | v = W_qkv LN1(x) + b_qkv;  per head S = scale Q K^T (scale =
+ *                                     head_dim^-1/2), P = softmax over the N keys, O = P V
+ *   x += W_2 relu(W_1 LN2(x) + b_1) + b_2
+ * x [B][N][D] fp32 dense -> y [B][N][D] fp32 dense, y must not overlap x.  Geometry: one workgroup of 16 waves owns one
+ * sample; its N <= 16 slot rows are one 16-row MFMA tile.  Rows >= N are supplied as zeros by the kernel (no memory
+ * behind row N - 1 is read) and never stored; keys >= N are excluded from every softmax.  The layers are looped inside
+ * the kernel.  The four projections are [16 x K] x [K x 16 n] products on mfma_f32_16x16x32_bf16 with the activations in
+ * LDS and the weights streamed from L2 in MFMA B-fragment order (kern.pred_pack_index, as sdmi_pred_step), the layers'
+ * operands concatenated (kern.pred_tf_pack):
+ *   wqkv [layers][3D x D], wo [layers][D x D], w1 [layers][F x D], w2 [layers][D x F]   bf16, packed
+ *   ln1_g ln1_b ln2_g ln2_b bo b2 [layers][D], bqkv [layers][3D], b1 [layers][F]         fp32
+ * Attention per head is a 16 x 16 score tile on the 16-deep bf16 MFMA (mfma_f32_16x16x16bf16_1k: head dims 16, 32, 48,
+ * 64 are 1..4 k steps, no padding of the k extent); the row softmax runs on the accumulator layout (a row's 16 keys are
+ * the 16 lanes of a lane group).
+ * Rounding points: the residual stream, LayerNorm (two-pass variance), the scores, the softmax, the accumulators and
+ * every output are fp32; a value is rounded to bf16 exactly once, where it feeds an MFMA: LN1(x); q, k, v; the softmax
+ * probabilities; the attention output O; LN2(x); the hidden layer.
+ * 1 <= N <= 16; D % 32 == 0, D <= 256; head_dim = D / heads a multiple of 16, <= 64; F % 32 == 0, F <= 1024;
+ * 1 <= layers <= 4 (kern.pred_tf_covers).  Speed against the composed chain: profiles/extract_bench.json. */
+typedef struct {
+  const float* x; float* y;
+  const void* wqkv; const void* wo; const void* w1; const void* w2;
+  const float* ln1_g; const float* ln1_b; const float* bqkv; const float* bo;
+  const float* ln2_g; const float* ln2_b; const float* b1; const float* b2;
+  int B, N, D, heads, F, layers; float eps;
+} SdmiPredTfArgs;
+int sdmi_pred_tf(const SdmiPredTfArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

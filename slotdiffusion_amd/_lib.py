@@ -197,6 +197,15 @@ def _log_call(fname, kw, meta):
         _CALL_LOG.flush()
 
 
+def set_call_log(path):
+    """Start (path: appended to) or stop (None) the SDMI_CALL_LOG record from inside a process -- measurement tools that
+    count the calls of one region and time another."""
+    global _CALL_LOG
+    if _CALL_LOG:
+        _CALL_LOG.close()
+    _CALL_LOG = open(path, 'a') if path else False
+
+
 def call(fname, stream, **kw):
     """Invoke `fname` with its argument struct filled from keyword args (missing fields = 0).
     `_meta` (optional dict: flops / bytes of the launch) only feeds KernelTimer."""

@@ -1,5 +1,10 @@
-// SAVi slot transition (sdmi.h: sdmi_lstm_cell / sdmi_lstm_cell_bwd / sdmi_pred_step; the reference's
-// video_based/models/predictor.py:47-73 ResidualMLPPredictor and 76-135 RNNPredictorWrapper).
+// SAVi slot transition (sdmi.h: sdmi_lstm_cell / sdmi_lstm_cell_bwd / sdmi_pred_step / sdmi_pred_tf; the reference's
+// video_based/models/predictor.py:20-44 TransformerPredictor, 47-73 ResidualMLPPredictor and 76-135
+// RNNPredictorWrapper).
+//
+// sdmi_pred_tf: the transformer transition, all layers in one launch -- described at pred_tf_kernel below.  Attention
+//   uses the 16-deep bf16 MFMA (hipcc --offload-arch=gfx950 accepts __builtin_amdgcn_mfma_f32_16x16x16bf16_1k), so a
+//   head dim of 48 is three k steps and nothing is zero-padded in LDS.
 //
 // sdmi_lstm_cell / _bwd: one thread per (row, hidden unit) -- the gate arithmetic around the GEMM that sdmi_igemm does.
 //
@@ -88,11 +93,11 @@ __device__ __forceinline__ void ps_batch(const bf16_t* ap, const uint4* wp, int 
 }
 
 // acc[g] += A[16 x 32 ks] (LDS, `lda` elements per row) x the packed fragments wp[(s NB + g) 64 + lane], s < ks, g < NB
-template <int NB>
+template <int NB, int INFLIGHT = PS_INFLIGHT>
 __device__ __forceinline__ void ps_dot(const bf16_t* A, int lda, const uint4* wp, int ks, int lane, f32x4* acc) {
   const bf16_t* ap = A + (lane & 15) * lda + 8 * (lane >> 4);
   wp += lane;
-  constexpr int U = PS_INFLIGHT / NB;
+  constexpr int U = INFLIGHT / NB;
   int s = 0;
   for (; s + U <= ks; s += U) ps_batch<NB, U>(ap, wp, s, acc);
   if constexpr (U >= 8) if (s + 8 <= ks) { ps_batch<NB, 8>(ap, wp, s, acc); s += 8; }
@@ -231,6 +236,194 @@ __global__ __launch_bounds__(64 * PS_WAVES) void pred_step_kernel(SdmiPredStepAr
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// fused transformer transition
+// ------------------------------------------------------------------------------------------
+typedef short tf_bf16x4 __attribute__((ext_vector_type(4)));
+constexpr int TF_LDP = 24;      // row pitch of the 16-key tiles (P, V^T): 48 bytes, 8-byte fragments stay aligned
+constexpr int TF_INFLIGHT = 8;  // weight fragments in flight: with 16 the kernel spills at the 128 VGPRs of a 16-wave workgroup
+
+// LayerNorm of slot row `wave` (fp32, two-pass; the arithmetic of pred_step_kernel's stage 0) -> A0 (bf16).  first: the
+// row comes from global memory (zeros past row N) and is copied into the residual stream
+__device__ __forceinline__ void tf_layer_norm(const float* xg, float* xres, bf16_t* A0, int ld0, int D, int N, bool first,
+                                              const float* g, const float* b, float eps, int wave, int lane) {
+  const int r = wave;
+  float v[4];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    v[k] = 0.f;
+    if (c < D) {
+      if (first) {
+        v[k] = r < N ? xg[(size_t)r * D + c] : 0.f;
+        xres[r * D + c] = v[k];
+      } else {
+        v[k] = xres[r * D + c];
+      }
+    }
+    s += v[k];
+  }
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float d = (lane + 64 * k < D) ? v[k] - mean : 0.f;
+    q = fmaf(d, d, q);
+  }
+  const float rstd = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    if (c < D) A0[r * ld0 + c] = f32_to_bf16(fmaf((v[k] - mean) * rstd, g[c], b[c]));
+  }
+}
+
+// sdmi_pred_tf: a workgroup of 16 waves owns ONE sample (its N <= 16 slot rows are one MFMA tile; rows past N are zeros
+// on the way in and never stored).  The residual stream stays in LDS in fp32 across the layers.  Per layer:
+//     stage 0  LN1 (a wave per row)                            -> A0 (bf16)
+//     stage 1  q | k | v = Wqkv A0 + bqkv                      -> QK [16][2D] and V transposed, Vt [D][16 keys] (bf16)
+//     stage 2  wave h < heads: S = scale Q_h K_h^T on the 16-deep bf16 MFMA (head_dim / 16 k steps: 48 needs no pad),
+//              keys past N masked, row softmax inside the accumulator (a row's 16 keys = the 16 lanes of a lane group)
+//                                                              -> P_h (bf16)
+//     stage 3  column chunk n of O = P V (one 16-deep MFMA)    -> A0 (bf16)
+//     stage 4  x += Wo A0 + bo                                 (fp32, LDS)
+//     stage 5  LN2                                             -> A0
+//     stage 6  hidden = relu(W1 A0 + b1)                       -> Hd (bf16; over QK / Vt / P, dead by now)
+//     stage 7  x += W2 hidden + b2                             (the last layer stores rows < N to y instead)
+//   The projections are ps_dot on the packed operands of pred_step_kernel, the layers' operands one behind the other.
+__global__ __launch_bounds__(64 * PS_WAVES) void pred_tf_kernel(SdmiPredTfArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tf_smem[];
+  const int D = p.D, F = p.F, N = p.N, heads = p.heads, hd = D / heads;
+  const int ld0 = D + PS_PAD, ldq = 2 * D + PS_PAD, ldh = F + PS_PAD;
+  float* xres = reinterpret_cast<float*>(tf_smem);                       // [16][D]
+  bf16_t* A0 = reinterpret_cast<bf16_t*>(xres + PS_ROWS * D);            // [16][ld0]
+  bf16_t* QK = A0 + PS_ROWS * ld0;                                       // [16][ldq]
+  bf16_t* Vt = QK + PS_ROWS * ldq;                                       // [D][TF_LDP]
+  bf16_t* Pb = Vt + D * TF_LDP;                                          // [heads][16][TF_LDP]
+  bf16_t* Hd = QK;                                                       // [16][ldh]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, rq = 4 * (lane >> 4);
+  const float* xg = p.x + (size_t)blockIdx.x * N * D;
+  float* yg = p.y + (size_t)blockIdx.x * N * D;
+  const float scale = 1.f / sqrtf((float)hd);
+  const int ksd = D >> 5, ksf = F >> 5;
+
+  for (int l = 0; l < p.layers; ++l) {
+    // ---- stage 0
+    tf_layer_norm(xg, xres, A0, ld0, D, N, l == 0, p.ln1_g + l * D, p.ln1_b + l * D, p.eps, wave, lane);
+    __syncthreads();
+    // ---- stage 1
+    {
+      const uint4* w = reinterpret_cast<const uint4*>(p.wqkv) + (size_t)l * 3 * D * D / 8;
+      const float* bias = p.bqkv + l * 3 * D;
+      for (int n = wave; n < (3 * D) >> 4; n += PS_WAVES) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        ps_dot<1, TF_INFLIGHT>(A0, ld0, w + (size_t)n * ksd * 64, ksd, lane, &acc);
+        const int c = 16 * n + col;
+        const float b = bias[c];
+        if (c < 2 * D) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) QK[(rq + j) * ldq + c] = f32_to_bf16(acc[j] + b);
+        } else {
+          uint2 v;
+          v.x = f32x2_to_bf16x2(acc[0] + b, acc[1] + b);
+          v.y = f32x2_to_bf16x2(acc[2] + b, acc[3] + b);
+          *reinterpret_cast<uint2*>(Vt + (c - 2 * D) * TF_LDP + rq) = v;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- stage 2
+    if (wave < heads) {
+      const bf16_t* qp = QK + col * ldq + wave * hd + rq;
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < hd; k += 16) {
+        const tf_bf16x4 a = *reinterpret_cast<const tf_bf16x4*>(qp + k);
+        const tf_bf16x4 b = *reinterpret_cast<const tf_bf16x4*>(qp + D + k);
+        s = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, s, 0, 0, 0);
+      }
+      bf16_t* pw = Pb + wave * PS_ROWS * TF_LDP;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = col < N ? s[j] * scale : -INFINITY;
+        float m = v;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        const float e = __expf(v - m);
+        float t = e;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        pw[(rq + j) * TF_LDP + col] = f32_to_bf16(e / t);
+      }
+    }
+    __syncthreads();
+    // ---- stage 3
+    for (int n = wave; n < D >> 4; n += PS_WAVES) {
+      const int h = (16 * n) / hd;
+      const tf_bf16x4 a = *reinterpret_cast<const tf_bf16x4*>(Pb + (h * PS_ROWS + col) * TF_LDP + rq);
+      const tf_bf16x4 b = *reinterpret_cast<const tf_bf16x4*>(Vt + (16 * n + col) * TF_LDP + rq);
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+      o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, o, 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) A0[(rq + j) * ld0 + 16 * n + col] = f32_to_bf16(o[j]);
+    }
+    __syncthreads();
+    // ---- stage 4
+    {
+      const uint4* w = reinterpret_cast<const uint4*>(p.wo) + (size_t)l * D * D / 8;
+      for (int n = wave; n < D >> 4; n += PS_WAVES) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        ps_dot<1, TF_INFLIGHT>(A0, ld0, w + (size_t)n * ksd * 64, ksd, lane, &acc);
+        const int c = 16 * n + col;
+        const float b = p.bo[l * D + c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xres[(rq + j) * D + c] = acc[j] + b + xres[(rq + j) * D + c];
+      }
+    }
+    __syncthreads();
+    // ---- stage 5
+    tf_layer_norm(xg, xres, A0, ld0, D, N, false, p.ln2_g + l * D, p.ln2_b + l * D, p.eps, wave, lane);
+    __syncthreads();
+    // ---- stage 6
+    {
+      const uint4* w = reinterpret_cast<const uint4*>(p.w1) + (size_t)l * F * D / 8;
+      for (int n = wave; n < F >> 4; n += PS_WAVES) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        ps_dot<1, TF_INFLIGHT>(A0, ld0, w + (size_t)n * ksd * 64, ksd, lane, &acc);
+        const float b = p.b1[l * F + 16 * n + col];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Hd[(rq + j) * ldh + 16 * n + col] = f32_to_bf16(fmaxf(acc[j] + b, 0.f));
+      }
+    }
+    __syncthreads();
+    // ---- stage 7
+    {
+      const uint4* w = reinterpret_cast<const uint4*>(p.w2) + (size_t)l * D * F / 8;
+      const bool last = l + 1 == p.layers;
+      for (int n = wave; n < D >> 4; n += PS_WAVES) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        ps_dot<1, TF_INFLIGHT>(Hd, ldh, w + (size_t)n * ksf * 64, ksf, lane, &acc);
+        const int c = 16 * n + col;
+        const float b = p.b2[l * D + c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float o = acc[j] + b + xres[(rq + j) * D + c];
+          if (!last) xres[(rq + j) * D + c] = o;
+          else if (rq + j < N) yg[(size_t)(rq + j) * D + c] = o;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+int tf_smem_bytes(int D, int F, int heads) {
+  const int attn = (PS_ROWS * (2 * D + PS_PAD) + D * TF_LDP + heads * PS_ROWS * TF_LDP) * 2;
+  const int ffn = PS_ROWS * (F + PS_PAD) * 2;
+  return PS_ROWS * D * 4 + PS_ROWS * (D + PS_PAD) * 2 + (attn > ffn ? attn : ffn);
+}
+
 int lc_blocks(long long n) {
   const long long b = (n + 255) / 256;
   return (int)(b > 2048 ? 2048 : b);
@@ -280,4 +473,28 @@ extern "C" int sdmi_pred_step(const SdmiPredStepArgs* a, void* stream) {
   const int tiles = (a->R + PS_ROWS - 1) / PS_ROWS;
   hipLaunchKernelGGL(pred_step_kernel, dim3(tiles), dim3(64 * PS_WAVES), smem, (hipStream_t)stream, k);
   return sdmi_check_launch("sdmi_pred_step");
+}
+
+extern "C" int sdmi_pred_tf(const SdmiPredTfArgs* a, void* stream) {
+  SDMI_REQUIRE(a && a->x && a->y, "null x / y");
+  SDMI_REQUIRE(a->B >= 1, "empty batch");
+  SDMI_REQUIRE(a->N >= 1 && a->N <= PS_ROWS, "1 <= N <= 16");
+  SDMI_REQUIRE(a->D >= 32 && a->D <= 256 && a->D % 32 == 0, "D must be a multiple of 32, at most 256");
+  SDMI_REQUIRE(a->heads >= 1 && a->D % a->heads == 0 && (a->D / a->heads) % 16 == 0 && a->D / a->heads <= 64,
+               "head_dim = D / heads must be a multiple of 16, at most 64");
+  SDMI_REQUIRE(a->F >= 32 && a->F <= 1024 && a->F % 32 == 0, "F must be a multiple of 32, at most 1024");
+  SDMI_REQUIRE(a->layers >= 1 && a->layers <= 4, "1 <= layers <= 4");
+  SDMI_REQUIRE(a->wqkv && a->wo && a->w1 && a->w2 && a->ln1_g && a->ln1_b && a->bqkv && a->bo && a->ln2_g && a->ln2_b &&
+               a->b1 && a->b2, "null operand");
+  SDMI_REQUIRE((((uintptr_t)a->wqkv | (uintptr_t)a->wo | (uintptr_t)a->w1 | (uintptr_t)a->w2) & 15) == 0,
+               "packed weights must be 16-byte aligned");
+  {
+    const uintptr_t x0 = (uintptr_t)a->x, y0 = (uintptr_t)a->y;
+    const unsigned long long n = (unsigned long long)a->B * a->N * a->D * 4;
+    SDMI_REQUIRE(x0 + n <= y0 || y0 + n <= x0, "y must not overlap x");
+  }
+  SDMI_OPTIN_LDS(pred_tf_kernel, 96 * 1024, "sdmi_pred_tf");
+  hipLaunchKernelGGL(pred_tf_kernel, dim3(a->B), dim3(64 * PS_WAVES), tf_smem_bytes(a->D, a->F, a->heads),
+                     (hipStream_t)stream, *a);
+  return sdmi_check_launch("sdmi_pred_tf");
 }

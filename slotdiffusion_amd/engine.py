@@ -202,11 +202,12 @@ def lstm_wrapper(K, u, state, name):
     return y, (h, c)
 
 
-def slot_transition(K, x, pred_dict, state, name='predictor'):
+def slot_transition(K, x, pred_dict, state, name='predictor', transformer=None):
     """The slot transition of SAVi / SAViDiffusion (savi.py:320-347) on x [B, N, D] fp32 -> [B, N, D] fp32; `state` is
     the model's PredictorState (used with pred_rnn only).  Inference on a bf16 model inside the kernel's geometry: ONE
     sdmi_pred_step launch (behind the transformer's launches when that is the base predictor); otherwise the composed
-    chain of K.ln / K.linear / K.lstm_cell launches, which records gradients under KernGrad."""
+    chain of K.ln / K.linear / K.lstm_cell launches, which records gradients under KernGrad.  `transformer`: what runs
+    the transformer base predictor (default transformer_predictor; stream_transition hands in the fused launch)."""
     B, N, D = x.shape
     mlp, rnn = spec.pred_is_mlp(pred_dict), bool(pred_dict.get('pred_rnn', False))
     base = spec.pred_base_name(pred_dict, name)
@@ -214,7 +215,8 @@ def slot_transition(K, x, pred_dict, state, name='predictor'):
     if rnn:
         x, hidden = state.enter(x)
     if not mlp:
-        x = transformer_predictor(K, x, pred_dict['pred_num_layers'], pred_dict['pred_num_heads'], name=base)
+        run = transformer or transformer_predictor
+        x = run(K, x, pred_dict['pred_num_layers'], pred_dict['pred_num_heads'], name=base)
         if not rnn:
             return x
     rows = x.reshape(B * N, D)
@@ -229,6 +231,62 @@ def slot_transition(K, x, pred_dict, state, name='predictor'):
     if rnn:
         state.leave(hidden)
     return y.view(B, N, D)
+
+
+# ------------------------------------------------------------------------------------------
+# whole-video slot extraction: the recurrence of savi.py:366-397 as a stream of chunks (savi.py:402-443 walks long
+# videos in pieces; video_based/extract_slots.py:18-37 is the caller).  Inference only.
+# ------------------------------------------------------------------------------------------
+def stream_transition(K, x, pred_dict, state, name='predictor'):
+    """slot_transition for the stream: a transformer base predictor inside kern.pred_tf_covers on a bf16 model is ONE
+    sdmi_pred_tf launch (slot_transition's own wrapper tail follows it with pred_rnn: sdmi_pred_step in RNN mode);
+    everything else, and everything with kern._PRED_TF off, is slot_transition as the clip encode runs it."""
+    from . import kern
+    if not kern._PRED_TF:
+        return slot_transition(K, x, pred_dict, state, name)
+
+    def fused_or_composed(K, x, num_layers, num_heads, name):
+        y = K.pred_tf(x, name, num_layers, num_heads)
+        return y if y is not None else transformer_predictor(K, x, num_layers, num_heads, name=name)
+    return slot_transition(K, x, pred_dict, state, name, transformer=fused_or_composed)
+
+
+def stream_keys_values(model, img):
+    """img [B, Tc, 3, H, W] -> Slot Attention's k | v of every frame, [Tc, B, M, 2 D] in compute dtype: the encoder, the
+    norm_inputs LayerNorm and the K/V projection ONCE over the B Tc frames (time-major, so a frame's batch is one
+    contiguous block for the fused Slot Attention launch)."""
+    B, T = img.shape[:2]
+    K = model.K()
+    name = 'slot_attention'
+    frames = img.transpose(0, 1).reshape((T * B,) + tuple(img.shape[2:]))
+    tok = encoder_out(K, model._to_nhwc(frames), model.rplan)
+    x = K.ln(tok, f'{name}.norm_inputs')
+    kv = K.linear(x, (f'{name}.project_k.weight', f'{name}.project_v.weight'))
+    return kv.view(T, B, kv.shape[1], kv.shape[2])
+
+
+def stream_recurrence(model, kv, prev_slots=None):
+    """The loop over frames on kv [Tc, B, M, 2 D]: stream_transition + the fused Slot Attention launch per frame (the
+    first frame of a video starts from the learnt init_latents, savi.py:377-380) -> slots [B, Tc, N, D] fp32."""
+    K = model.K()
+    out = []
+    for t in range(kv.shape[0]):
+        if prev_slots is None:
+            lat = model.init_latents[0]
+        else:
+            lat = stream_transition(K, prev_slots.contiguous(), model.pred_dict, model.pred_state)
+        prev_slots, _ = K.slot_attention(kv[t], lat, 'slot_attention', model.num_iterations, model.eps)
+        out.append(prev_slots)
+    return K.stack_time(out)
+
+
+def encode_stream(model, img, prev_slots=None):
+    """One chunk of a video model's encode for extraction: img [B, Tc, 3, H, W], prev_slots [B, N, D] fp32 (the last
+    slots of the chunk before) or None (a new video: the learnt init_latents, and the wrapper's state is cleared,
+    savi.py:453-455) -> slots [B, Tc, N, D] fp32.  stream_keys_values, then stream_recurrence.  Records no gradient."""
+    model.pred_state.begin_forward(prev_slots)
+    with torch.no_grad():
+        return stream_recurrence(model, stream_keys_values(model, img), prev_slots)
 
 
 # ------------------------------------------------------------------------------------------

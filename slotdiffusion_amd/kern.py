@@ -269,6 +269,40 @@ def pred_pack(W, base, wrap, device=None):
     return out
 
 
+# the transformer slot transition (predictor.py:20-44) as ONE sdmi_pred_tf launch in engine.encode_stream: bf16 inference
+# inside this geometry.  Off (tests, tools/bench_extract.py): the stream runs engine.slot_transition, so both sides of an
+# A/B run in one process.  Like _PRED_FUSED not a policy switch: the policy table is at the size test_host_cpu.py caps.
+_PRED_TF = True
+_PRED_TF_MATS = (('wqkv', 'self_attn.in_proj_weight'), ('wo', 'self_attn.out_proj.weight'), ('w1', 'linear1.weight'),
+                 ('w2', 'linear2.weight'))
+_PRED_TF_VECS = (('ln1_g', 'norm1.weight'), ('ln1_b', 'norm1.bias'), ('bqkv', 'self_attn.in_proj_bias'),
+                 ('bo', 'self_attn.out_proj.bias'), ('ln2_g', 'norm2.weight'), ('ln2_b', 'norm2.bias'),
+                 ('b1', 'linear1.bias'), ('b2', 'linear2.bias'))
+
+
+def pred_tf_covers(N, D, heads, ffn, layers):
+    """Geometry of sdmi_pred_tf (sdmi.h): one 16-row tile of slots, head dims on the 16-deep MFMA, inside its LDS
+    budget."""
+    if heads < 1 or D % heads:
+        return False
+    hd = D // heads
+    return (1 <= N <= 16 and 32 <= D <= 256 and D % 32 == 0 and hd % 16 == 0 and hd <= 64 and
+            32 <= ffn <= 1024 and ffn % 32 == 0 and 1 <= layers <= 4)
+
+
+def pred_tf_pack(W, base, layers, device=None):
+    """Operands of sdmi_pred_tf out of a {key: tensor} dict: `base` = key prefix of the TransformerPredictor.  Every
+    matrix is rounded to bf16 and packed (pred_pack_index), the layers' operands one behind the other; the vectors are
+    fp32 [layers, n].  F = ffn width."""
+    dev = device or next(iter(W.values())).device
+    f = lambda i, k: W[f'{base}.transformer_encoder.layers.{i}.{k}'].detach().to(dev).float().contiguous()
+    pk = lambda w: w.to(torch.bfloat16).reshape(-1)[pred_pack_index(w.shape[0], w.shape[1], 1, dev)]
+    out = {k: torch.cat([pk(f(i, n)) for i in range(layers)]).contiguous() for k, n in _PRED_TF_MATS}
+    out.update({k: torch.stack([f(i, n) for i in range(layers)]).contiguous() for k, n in _PRED_TF_VECS})
+    out.update(F=out['b1'].shape[1], layers=layers)
+    return out
+
+
 def st_train_units(C):
     """Unit order of the training kernels' weight streams (csrc/st_train.hip), per wave: lists of
     (matrix key, first row, first k, transposed).  Forward: a = [proj_in | q | k | v], b = [to_out | q2 | to_out2 | per
@@ -716,6 +750,15 @@ class WeightBank:
         if key not in self.cache:
             with torch.no_grad():
                 self.cache[key] = pred_pack(self.t, base, wrap)
+        return self.cache[key]
+
+    def pred_tf_weights(self, base, layers):
+        """Packed operands of the fused transformer transition (pred_tf_pack) from the master weights, rounded to bf16
+        as the shadow arena rounds them.  Weight preparation, cached until the weights change."""
+        key = ('pred_tf', base, layers)
+        if key not in self.cache:
+            with torch.no_grad():
+                self.cache[key] = pred_tf_pack(self.t, base, layers)
         return self.cache[key]
 
     # ---- weight streams of the fused SpatialTransformer TRAINING kernels (sdmi.h: sdmi_st_train_fwd, sdmi_st_pack)
@@ -1187,6 +1230,16 @@ class Kern:
         h, c = state if state is not None else (None, None)
         y, h, c = ops.pred_step(x, self.wb.pred_step_weights(base, wrap), mode, norm_first, h, c)
         return y, ((h, c) if wrap else None)
+
+    def pred_tf(self, x, base, layers, heads):
+        """The transformer slot transition as ONE sdmi_pred_tf launch: x [B, N, D] fp32, `base` = key prefix of the
+        TransformerPredictor -> [B, N, D] fp32; None when the launch does not apply (the caller runs
+        engine.transformer_predictor): fp32 model, geometry outside pred_tf_covers."""
+        B, N, D = x.shape
+        F = self.wb.t[f'{base}.transformer_encoder.layers.0.linear1.weight'].shape[0]
+        if not (self.wb.dtype == torch.bfloat16 and x.dtype == torch.float32 and pred_tf_covers(N, D, heads, F, layers)):
+            return None
+        return ops.pred_tf(x.contiguous(), self.wb.pred_tf_weights(base, layers), heads)
 
     def cast_pad(self, x, dtype, cols, ldd):
         """First `cols` channels of x [..., ld] -> dtype [..., ldd] (zero padded)."""
@@ -2702,6 +2755,9 @@ class KernGrad(Kern):
 
     def pred_step(self, x, base, wrap, norm_first, state):
         return None                         # (recording gradients: the composed chain is the training path)
+
+    def pred_tf(self, x, base, layers, heads):
+        return None                         # (as pred_step)
 
     def cast_pad(self, x, dtype, cols, ldd):
         return CastPadFn.apply(x, dtype, cols, ldd)

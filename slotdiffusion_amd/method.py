@@ -62,6 +62,39 @@ class SyntheticSlotsDataModule:
             yield {'slots': torch.randn(shape, generator=g).to(self.device)}
 
 
+class SlotsFileDataModule:
+    """Slots of a file written by extract.dump_slots (the reference's slots.pkl, video_based/extract_slots.py:50-62) as
+    the vp_vqa task's input, with SyntheticSlotsDataModule's `train_loader(epoch)` contract: {'slots': [B, history_len +
+    rollout_len, N, D]}, each a contiguous window of one stored video drawn by a generator seeded per (seed, epoch,
+    rank)."""
+
+    def __init__(self, params, path, split='train', steps_per_epoch=8, device='cuda', seed=1234):
+        from .extract import load_slots
+        self.params, self.steps_per_epoch, self.device, self.seed = params, steps_per_epoch, device, seed
+        self.rank = int(os.environ.get('RANK', 0))
+        data = load_slots(path)[split]
+        self.T = params.rollout_dict['history_len'] + params.loss_dict['rollout_len']
+        self.files = [f for f in sorted(data) if data[f].shape[0] >= self.T]        # shorter videos hold no window
+        self.videos = [torch.as_tensor(data[f]).float() for f in self.files]
+        assert self.videos, f'{path} [{split}]: no video has {self.T} frames'
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def windows(self, epoch=0):
+        """The (video index, first frame) pairs of an epoch, [steps][B]: what train_loader cuts."""
+        g = torch.Generator().manual_seed(self.seed + 1000 * epoch + self.rank)
+        out = []
+        for _ in range(self.steps_per_epoch):
+            vi = torch.randint(len(self.videos), (self.params.train_batch_size,), generator=g).tolist()
+            out.append([(v, int(torch.randint(self.videos[v].shape[0] - self.T + 1, (1,), generator=g))) for v in vi])
+        return out
+
+    def train_loader(self, epoch=0):
+        for step in self.windows(epoch):
+            yield {'slots': torch.stack([self.videos[v][t0:t0 + self.T] for v, t0 in step]).to(self.device)}
+
+
 class SyntheticSlotsLabelDataModule:
     """`build_dataset` stand-in of the VQA readout (vp_vqa/datasets/physion.py: physion_slots_label_readout): seeded
     random slots [B, video_len, N, D] with a 0 / 1 label that follows a planted rule the readout can represent --

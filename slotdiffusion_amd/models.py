@@ -874,6 +874,11 @@ class SAViDiffusion(SADiffusion):
         """savi_diffusion.py:169-216: img [B,T,3,H,W] -> slots [B,T,N,D], masks [B,T,N,*,*]."""
         return _encode_clip(self, img, prev_slots)
 
+    @torch.no_grad()
+    def encode_stream(self, img, prev_slots=None):
+        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]."""
+        return engine.encode_stream(self, img, prev_slots)
+
     def calc_train_loss(self, data_dict, out_dict):
         """savi_diffusion.py:252-264: the LDM sees the B*T frames as independent images."""
         d = {'img': data_dict['img'].flatten(0, 1), 'slots': out_dict['slots'].flatten(0, 1)}
@@ -1009,6 +1014,11 @@ class SAVi(SA):
     def encode(self, img, prev_slots=None):
         """savi.py:366-397: img [B,T,3,H,W] -> slots [B,T,N,D]."""
         return _encode_clip(self, img, prev_slots)[0]
+
+    @torch.no_grad()
+    def encode_stream(self, img, prev_slots=None):
+        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]."""
+        return engine.encode_stream(self, img, prev_slots)
 
     def forward(self, data_dict):
         """savi.py:445-475 (clips longer than clip_len are not split: 288 GB of HBM)."""

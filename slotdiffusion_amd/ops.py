@@ -983,3 +983,17 @@ def pred_step(x, W, mode, norm_first=True, h_prev=None, c_prev=None, eps=1e-5):
          wop=g('wop'), bo=g('bo'), R=R, D=D, H=H, ldx=_pitch(x), ldh=_pitch(h_prev), mode=mode,
          norm_first=int(bool(norm_first)), eps=eps)
     return y, h, c
+
+
+def pred_tf(x, W, heads, eps=1e-5):
+    """The fused transformer transition: x [B, N, D] fp32 contiguous, W = dict of the packed bf16 operands and fp32
+    vectors (kern.pred_tf_pack) -> y [B, N, D] fp32."""
+    _need_gpu(x)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    B, N, D = x.shape
+    F, L = W['F'], W['layers']
+    y = torch.empty_like(x)
+    call('sdmi_pred_tf', _stream(), x=_p(x), y=_p(y), B=B, N=N, D=D, heads=heads, F=F, layers=L, eps=eps,
+         **{k: _p(W[k]) for k in ('wqkv', 'wo', 'w1', 'w2', 'ln1_g', 'ln1_b', 'bqkv', 'bo', 'ln2_g', 'ln2_b', 'b1', 'b2')},
+         _meta=dict(flops=2.0 * B * L * 16 * (4 * D * D + 2 * D * F), bytes=float(2 * L * (4 * D * D + 2 * D * F) + 8 * B * N * D)))
+    return y
