@@ -665,6 +665,33 @@ typedef struct {
 } SdmiRolloutLayerArgs;
 int sdmi_rollout_layer(const SdmiRolloutLayerArgs* a, void* stream);
 
+/* Everything between the last layer of rollout step s and the first layer of step s + 1 as ONE launch (bf16 inference;
+ * vp_vqa/models/slotformer.py:112-124: take the last N output tokens, out_proj, feed the prediction back through in_proj,
+ * slide the window, add the positions).  One workgroup of 16 waves owns one sequence; its N <= 16 newest token rows are
+ * one MFMA tile.
+ *   pred = Wout x[L-N .. L) + bout                       fp32, stored; rounded ONCE to bf16 where it feeds in_proj
+ *   tok  = bf16(Win bf16(pred) + bin)                    fp32 accumulation, one storage rounding
+ *   win_next rows [0, L-N) = win rows [N, L), rows [L-N, L) = tok;  x_next = bf16(float(win_next) + pos)
+ * -- the rounding points of sdmi_cast + sdmi_igemm (bf16 out) + sdmi_add_pos, which it replaces together with the row
+ * copies around them.  Both products run on mfma_f32_16x16x32_bf16 with the weights streamed in MFMA B-fragment order
+ * (kern.pred_pack_index, as sdmi_pred_step).  Rows of the tile past N are zeros inside the kernel; no memory outside the
+ * rows named below is read or written.
+ * 1 <= N <= 16; L a multiple of N, N <= L <= Lp; C and Ds multiples of 32 within 32 .. 256 (kern.rollout_feed_covers).
+ * x_next and win_next must not overlap x, win or each other.  Speed against the composed glue:
+ * profiles/rollout_stage_bench.json. */
+typedef struct {
+  const void* x;          /* [B][Lp][C] bf16: output of the last layer; only rows [L-N, L) are read          */
+  const void* win;        /* [B][Lp][C] bf16: current window WITHOUT positions; NULL = last step (pred only) */
+  void* win_next;         /* [B][Lp][C] bf16: rows [0,L-N) = win rows [N,L); rows [L-N,L) = tok; rows >= L untouched */
+  void* x_next;           /* [B][Lp][C] bf16: rows < L = bf16(float(win_next) + pos); rows [L,Lp) = 0         */
+  const float* pos;       /* [Lp][C] fp32 (engine.rollout_pos)                                               */
+  float* pred; long long ld_pred;   /* sample b writes [N][Ds] fp32 at pred + b*ld_pred (step s of [B,P,N,Ds]) */
+  const void* wout; const float* bout;   /* out_proj [Ds x C] bf16 in kern.pred_pack_index order; [Ds] fp32   */
+  const void* win_w; const float* bin;   /* in_proj  [C x Ds] packed likewise; [C] fp32                       */
+  int B, N, L, Lp, C, Ds;
+} SdmiRolloutFeedArgs;
+int sdmi_rollout_feed(const SdmiRolloutFeedArgs* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Physion VQA readout (PhysionReadout.forward + calc_train_loss, vp_vqa/models/readout.py:56-87): per frame, linear1 on
  * every slot pair [s_i | s_j] (i < j, itertools.combinations order), a symmetric aggregate over the pairs, linear2, then

@@ -1,6 +1,7 @@
 // SAVi slot transition (sdmi.h: sdmi_lstm_cell / sdmi_lstm_cell_bwd / sdmi_pred_step / sdmi_pred_tf; the reference's
 // video_based/models/predictor.py:20-44 TransformerPredictor, 47-73 ResidualMLPPredictor and 76-135
-// RNNPredictorWrapper).
+// RNNPredictorWrapper), and at the end of the file sdmi_rollout_feed, the per-step glue of the SlotFormer rollout on the
+// same ps_dot products -- described at rollout_feed_kernel.
 //
 // sdmi_pred_tf: the transformer transition, all layers in one launch -- described at pred_tf_kernel below.  Attention
 //   uses the 16-deep bf16 MFMA (hipcc --offload-arch=gfx950 accepts __builtin_amdgcn_mfma_f32_16x16x16bf16_1k), so a
@@ -497,4 +498,124 @@ extern "C" int sdmi_pred_tf(const SdmiPredTfArgs* a, void* stream) {
   hipLaunchKernelGGL(pred_tf_kernel, dim3(a->B), dim3(64 * PS_WAVES), tf_smem_bytes(a->D, a->F, a->heads),
                      (hipStream_t)stream, *a);
   return sdmi_check_launch("sdmi_pred_tf");
+}
+
+// ------------------------------------------------------------------------------------------
+// SlotFormer rollout: everything between the last layer of step s and the first layer of step s + 1
+// (vp_vqa/models/slotformer.py:112-124)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int RF_MAXD = 256;                                // largest C / Ds
+
+// sdmi_rollout_feed: a workgroup of 16 waves owns ONE sequence; its N <= 16 newest token rows are one MFMA tile (rows
+// past N are zeros on the way in and never stored).
+//     stage a  rows [L - N, L) of x                                   -> A0 (bf16, LDS)
+//     stage b  pred = Wout A0 + bout    (a wave per 16-column chunk)  -> pred (fp32, global), bf16(pred) -> A1 (LDS)
+//     stage c  tok = bf16(Win A1 + bin)                               -> A0 (LDS; its stage-a rows are dead by now)
+//     stage d  win_next = [win rows [N, L) | tok], x_next = bf16(win_next + pos), x_next rows [L, Lp) = 0: 16-byte
+//              accesses, all waves
+//   win == NULL (the last step) ends after stage b.  The products are ps_dot on operands packed as for pred_step_kernel.
+__global__ __launch_bounds__(64 * PS_WAVES) void rollout_feed_kernel(SdmiRolloutFeedArgs p) {
+  __shared__ __attribute__((aligned(16))) bf16_t A0[PS_ROWS * (RF_MAXD + PS_PAD)];
+  __shared__ __attribute__((aligned(16))) bf16_t A1[PS_ROWS * (RF_MAXD + PS_PAD)];
+  const int C = p.C, Ds = p.Ds, N = p.N, L = p.L;
+  const int ld0 = C + PS_PAD, ld1 = Ds + PS_PAD, cv = C >> 3;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, rq = 4 * (lane >> 4);
+  const size_t seq = (size_t)blockIdx.x * p.Lp * C;          // first element of this sequence's window
+
+  // ---- stage a
+  if (tid < PS_ROWS * cv) {
+    const int r = tid / cv, ch = tid - r * cv;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (r < N) v = *reinterpret_cast<const uint4*>((const bf16_t*)p.x + seq + (size_t)(L - N + r) * C + 8 * ch);
+    *reinterpret_cast<uint4*>(A0 + r * ld0 + 8 * ch) = v;
+  }
+  __syncthreads();
+  // ---- stage b
+  {
+    const int ks = C >> 5;
+    float* pg = p.pred + (long long)blockIdx.x * p.ld_pred;
+    for (int n = wave; n < Ds >> 4; n += PS_WAVES) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      ps_dot<1>(A0, ld0, reinterpret_cast<const uint4*>(p.wout) + (size_t)n * ks * 64, ks, lane, &acc);
+      const int c = 16 * n + col;
+      const float b = p.bout[c];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = acc[j] + b;
+        if (rq + j < N) pg[(rq + j) * Ds + c] = v;
+        A1[(rq + j) * ld1 + c] = f32_to_bf16(v);
+      }
+    }
+  }
+  if (!p.win) return;
+  __syncthreads();
+  // ---- stage c
+  {
+    const int ks = Ds >> 5;
+    for (int n = wave; n < C >> 4; n += PS_WAVES) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      ps_dot<1>(A1, ld1, reinterpret_cast<const uint4*>(p.win_w) + (size_t)n * ks * 64, ks, lane, &acc);
+      const int c = 16 * n + col;
+      const float b = p.bin[c];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) A0[(rq + j) * ld0 + c] = f32_to_bf16(acc[j] + b);
+    }
+  }
+  __syncthreads();
+  // ---- stage d
+  {
+    const bf16_t* wg = (const bf16_t*)p.win + seq;
+    bf16_t* wn = (bf16_t*)p.win_next + seq;
+    bf16_t* xn = (bf16_t*)p.x_next + seq;
+    const int keep = L - N;
+    for (int i = tid; i < L * cv; i += 64 * PS_WAVES) {
+      const int r = i / cv, ch = i - r * cv;
+      const size_t o = (size_t)r * C + 8 * ch;
+      uint4 v;
+      if (r < keep) v = *reinterpret_cast<const uint4*>(wg + o + (size_t)N * C);
+      else v = *reinterpret_cast<const uint4*>(A0 + (r - keep) * ld0 + 8 * ch);
+      *reinterpret_cast<uint4*>(wn + o) = v;
+      float f[8];
+      unpack16<bf16_t>(v, f);
+      const float4 p0 = *reinterpret_cast<const float4*>(p.pos + o);
+      const float4 p1 = *reinterpret_cast<const float4*>(p.pos + o + 4);
+      f[0] += p0.x; f[1] += p0.y; f[2] += p0.z; f[3] += p0.w;
+      f[4] += p1.x; f[5] += p1.y; f[6] += p1.z; f[7] += p1.w;
+      *reinterpret_cast<uint4*>(xn + o) = pack16<bf16_t>(f);
+    }
+    for (int i = L * cv + tid; i < p.Lp * cv; i += 64 * PS_WAVES)
+      *reinterpret_cast<uint4*>(xn + (size_t)i * 8) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+bool rf_disjoint(const void* a, const void* b, unsigned long long n) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 + n <= b0 || b0 + n <= a0;
+}
+
+}  // namespace
+
+extern "C" int sdmi_rollout_feed(const SdmiRolloutFeedArgs* a, void* stream) {
+  SDMI_REQUIRE(a && a->x && a->pred && a->wout && a->bout, "null x / pred / wout / bout");
+  SDMI_REQUIRE(a->B >= 1, "empty batch");
+  SDMI_REQUIRE(a->N >= 1 && a->N <= PS_ROWS, "1 <= N <= 16");
+  SDMI_REQUIRE(a->L >= a->N && a->L % a->N == 0 && a->L <= a->Lp, "L must be a multiple of N with N <= L <= Lp");
+  SDMI_REQUIRE(a->C >= 32 && a->C <= RF_MAXD && a->C % 32 == 0, "C must be a multiple of 32, at most 256");
+  SDMI_REQUIRE(a->Ds >= 32 && a->Ds <= RF_MAXD && a->Ds % 32 == 0, "Ds must be a multiple of 32, at most 256");
+  SDMI_REQUIRE(a->ld_pred >= (long long)a->N * a->Ds, "ld_pred shorter than a sample's [N][Ds]");
+  SDMI_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->wout) & 15) == 0, "x / wout must be 16-byte aligned");
+  if (a->win) {
+    SDMI_REQUIRE(a->win_next && a->x_next && a->pos && a->win_w && a->bin, "null win_next / x_next / pos / win_w / bin");
+    SDMI_REQUIRE((((uintptr_t)a->win | (uintptr_t)a->win_next | (uintptr_t)a->x_next | (uintptr_t)a->pos |
+                   (uintptr_t)a->win_w) & 15) == 0, "win / win_next / x_next / pos / win_w must be 16-byte aligned");
+    const unsigned long long n = (unsigned long long)a->B * a->Lp * a->C * 2;
+    SDMI_REQUIRE(rf_disjoint(a->x_next, a->x, n) && rf_disjoint(a->x_next, a->win, n) &&
+                 rf_disjoint(a->win_next, a->x, n) && rf_disjoint(a->win_next, a->win, n) &&
+                 rf_disjoint(a->win_next, a->x_next, n), "x_next / win_next must not overlap x, win or each other");
+  }
+  hipLaunchKernelGGL(rollout_feed_kernel, dim3(a->B), dim3(64 * PS_WAVES), 0, (hipStream_t)stream, *a);
+  return sdmi_check_launch("sdmi_rollout_feed");
 }

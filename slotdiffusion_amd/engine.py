@@ -312,14 +312,16 @@ def rollout_pos(K, name, T, N, Lp):
     return wb.cache[key]
 
 
-def slot_rollout(K, past_slots, pred_len, num_layers, num_heads, name='rollouter', fused=False):
+def slot_rollout(K, past_slots, pred_len, num_layers, num_heads, name='rollouter', fused=False, feed=False):
     """past_slots [B, T, N, Ds] fp32 -> predicted slots [B, pred_len, N, Ds] fp32.
 
     Every slot is projected ONCE (in_proj is row-wise, so the cached tokens equal a re-projection of the window); the
     temporal encoding belongs to the window position and is added anew every step.  fused (bf16 inference): the window
     lives in Lp = ceil(T N / 64) 64 rows and every layer is one sdmi_rollout_layer call (two launches); otherwise the
     layers are the per-layer launches of transformer_predictor (autograd-recording under KernGrad: gradients flow
-    through all steps)."""
+    through all steps).  feed (with fused, inside kern.rollout_feed_covers): everything between the last layer of a step
+    and the first layer of the next is ONE sdmi_rollout_feed launch -- the window ping-pongs between two buffers and
+    every step writes its slice of the result, so after the setup a step is num_layers + 1 calls."""
     B, T, N, Ds = past_slots.shape
     L = T * N
     dt = K.wb.dtype
@@ -331,6 +333,22 @@ def slot_rollout(K, past_slots, pred_len, num_layers, num_heads, name='rollouter
     win = tok
     if Lp != L:            # into the padded window (pad rows may hold anything: they never reach a real row)
         win = K.shift_window(torch.empty((B, Lp, D), dtype=tok.dtype, device=tok.device), tok, L)
+    if feed:
+        assert fused and num_layers >= 1, 'the feed kernel sits between fused layers (the caller checks)'
+        out = torch.empty((B, pred_len, N, Ds), dtype=torch.float32, device=tok.device)
+        x = K.add_pos(win, pe)
+        wins = (win, torch.empty_like(win))
+        for step in range(pred_len):
+            for i in range(num_layers):
+                x = K.rollout_layer(x, f'{name}.transformer_encoder.layers.{i}', L, num_heads)
+                assert x is not None, 'the caller checks that the layers qualify for the fused kernel'
+            if step + 1 < pred_len:
+                x_next = torch.empty_like(x)
+                K.rollout_feed(x, wins[step % 2], wins[(step + 1) % 2], x_next, pe, out, step, N, L, name)
+                x = x_next
+            else:
+                K.rollout_feed(x, None, None, None, pe, out, step, N, L, name)
+        return out
     preds = []
     for step in range(pred_len):
         x = K.add_pos(win, pe)

@@ -303,6 +303,30 @@ def pred_tf_pack(W, base, layers, device=None):
     return out
 
 
+# the glue between two steps of the fused SlotFormer rollout (tail tokens, out_proj, cast, in_proj, window shift, positions)
+# as ONE sdmi_rollout_feed launch in engine.slot_rollout(feed=True), which LDMSlotFormer.unroll takes for bf16 inference
+# inside rollout_feed_covers.  Off (tests, tools/bench_rollout_stage.py): unroll is rollout().  Like _PRED_TF not a policy
+# switch.
+_ROLLOUT_FEED = True
+
+
+def rollout_feed_covers(N, L, Lp, C, Ds):
+    """Geometry of sdmi_rollout_feed (sdmi.h): the N newest token rows are one 16-row tile, the window is whole steps of
+    N rows inside its Lp rows, both widths are multiples of the 32-deep MFMA inside the kernel's LDS arrays."""
+    return (1 <= N <= 16 and N <= L <= Lp and L % N == 0 and 32 <= C <= 256 and C % 32 == 0 and
+            32 <= Ds <= 256 and Ds % 32 == 0)
+
+
+def rollout_feed_pack(w_out, b_out, w_in, b_in, device=None):
+    """Operands of sdmi_rollout_feed: out_proj.weight [Ds, C] and in_proj.weight [C, Ds] rounded to bf16 and packed
+    (pred_pack_index), the biases fp32."""
+    dev = device or w_out.device
+    pk = lambda w: w.detach().to(dev).to(torch.bfloat16).reshape(-1)[
+        pred_pack_index(w.shape[0], w.shape[1], 1, dev)].contiguous()
+    f = lambda b: b.detach().to(dev).float().contiguous()
+    return dict(wout=pk(w_out), bout=f(b_out), win_w=pk(w_in), bin=f(b_in), C=w_out.shape[1], Ds=w_out.shape[0])
+
+
 def st_train_units(C):
     """Unit order of the training kernels' weight streams (csrc/st_train.hip), per wave: lists of
     (matrix key, first row, first k, transposed).  Forward: a = [proj_in | q | k | v], b = [to_out | q2 | to_out2 | per
@@ -729,6 +753,17 @@ class WeightBank:
                 src_b = torch.cat([wo.to(dtype).reshape(-1), w1_p.reshape(-1), w2.to(dtype).reshape(-1)])
                 vb = torch.cat([bo, w1_p.float().sum(1), w1 @ b2 + bb1, bb2]).contiguous()
                 self.cache[key] = dict(wa=wa, va=va, wb=src_b[ib].contiguous(), vb=vb, C=C, F=F)
+        return self.cache[key]
+
+    def rollout_feed_weights(self, name):
+        """Packed operands of sdmi_rollout_feed for the rollouter `name` (rollout_feed_pack) from the master weights,
+        rounded to bf16 as the shadow arena rounds them.  Weight preparation, cached until the weights change."""
+        key = ('rollout_feed', name)
+        if key not in self.cache:
+            with torch.no_grad():
+                ip, op = f'{name}.in_proj', f'{name}.out_proj'
+                self.cache[key] = rollout_feed_pack(self.t[op + '.weight'], self.t[op + '.bias'],
+                                                    self.t[ip + '.weight'], self.t[ip + '.bias'])
         return self.cache[key]
 
     def readout_weights(self, dtype, name='linear1.weight'):
@@ -1182,6 +1217,22 @@ class Kern:
              ln_eps=1e-5, attn_scale=32.0 ** -0.5,
              _meta=dict(flops=flops, bytes=2.0 * B * Lp * C * 2 + 2.0 * (wts['wa'].numel() + wts['wb'].numel())))
         return out
+
+    def rollout_feed(self, x, win, win_next, x_next, pos, pred, step, N, L, name):
+        """The glue between rollout steps `step` and `step + 1` as ONE launch (sdmi.h: sdmi_rollout_feed): x [B, Lp, C]
+        bf16 = the last layer's output, win the window without positions (None: the last step, only pred is written),
+        pred [B, P, N, Ds] fp32 whose slice `step` is written; win_next / x_next [B, Lp, C] are filled for the next
+        step.  The caller checks rollout_feed_covers."""
+        B, Lp, C = x.shape
+        P, Ds = pred.shape[1], pred.shape[3]
+        wts = self.wb.rollout_feed_weights(name)
+        assert wts['C'] == C and wts['Ds'] == Ds and pred.is_contiguous() and x.is_contiguous()
+        last = win is None
+        call('sdmi_rollout_feed', _st(), x=_p(x), win=_p(win), win_next=0 if last else _p(win_next),
+             x_next=0 if last else _p(x_next), pos=_p(pos), pred=pred.data_ptr() + step * N * Ds * 4,
+             ld_pred=P * N * Ds, wout=_p(wts['wout']), bout=_p(wts['bout']), win_w=_p(wts['win_w']), bin=_p(wts['bin']),
+             B=B, N=N, L=L, Lp=Lp, C=C, Ds=Ds,
+             _meta=dict(flops=4.0 * B * N * C * Ds, bytes=4.0 * C * Ds + (0.0 if last else 6.0 * B * L * C)))
 
     def geglu(self, h):
         return ops.geglu(h)

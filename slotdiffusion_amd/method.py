@@ -65,18 +65,21 @@ class SyntheticSlotsDataModule:
 class SlotsFileDataModule:
     """Slots of a file written by extract.dump_slots (the reference's slots.pkl, video_based/extract_slots.py:50-62) as
     the vp_vqa task's input, with SyntheticSlotsDataModule's `train_loader(epoch)` contract: {'slots': [B, history_len +
-    rollout_len, N, D]}, each a contiguous window of one stored video drawn by a generator seeded per (seed, epoch,
-    rank)."""
+    rollout_len, N, D]}, each a window of one stored video drawn by a generator seeded per (seed, epoch, rank): frames
+    t0 + k frame_offset (physion.py's frame_offset; 1 = contiguous), t0 below len - (T - 1) frame_offset."""
 
-    def __init__(self, params, path, split='train', steps_per_epoch=8, device='cuda', seed=1234):
+    def __init__(self, params, path, split='train', steps_per_epoch=8, device='cuda', seed=1234, frame_offset=1):
         from .extract import load_slots
+        assert frame_offset >= 1
         self.params, self.steps_per_epoch, self.device, self.seed = params, steps_per_epoch, device, seed
         self.rank = int(os.environ.get('RANK', 0))
+        self.frame_offset = int(frame_offset)
         data = load_slots(path)[split]
         self.T = params.rollout_dict['history_len'] + params.loss_dict['rollout_len']
-        self.files = [f for f in sorted(data) if data[f].shape[0] >= self.T]        # shorter videos hold no window
+        self.span = (self.T - 1) * self.frame_offset + 1                            # frames a window reaches over
+        self.files = [f for f in sorted(data) if data[f].shape[0] >= self.span]     # shorter videos hold no window
         self.videos = [torch.as_tensor(data[f]).float() for f in self.files]
-        assert self.videos, f'{path} [{split}]: no video has {self.T} frames'
+        assert self.videos, f'{path} [{split}]: no video has {self.span} frames'
 
     def __len__(self):
         return self.steps_per_epoch
@@ -87,12 +90,90 @@ class SlotsFileDataModule:
         out = []
         for _ in range(self.steps_per_epoch):
             vi = torch.randint(len(self.videos), (self.params.train_batch_size,), generator=g).tolist()
-            out.append([(v, int(torch.randint(self.videos[v].shape[0] - self.T + 1, (1,), generator=g))) for v in vi])
+            out.append([(v, int(torch.randint(self.videos[v].shape[0] - self.span + 1, (1,), generator=g))) for v in vi])
         return out
 
     def train_loader(self, epoch=0):
+        fo = self.frame_offset
         for step in self.windows(epoch):
-            yield {'slots': torch.stack([self.videos[v][t0:t0 + self.T] for v, t0 in step]).to(self.device)}
+            yield {'slots': torch.stack([self.videos[v][t0:t0 + self.span:fo] for v, t0 in step]).to(self.device)}
+
+
+def physion_label_key(fname, split):
+    """The labels-CSV key of a stored video (vp_vqa/datasets/physion.py:316-324): the basename without `.mp4`, for the
+    readout subset (every split but 'test') without a trailing `_img`, for the test subset without `-redyellow`."""
+    key = os.path.basename(fname)
+    if key.endswith('.mp4'):
+        key = key[:-4]
+    if split != 'test' and key.endswith('_img'):
+        key = key[:-4]
+    if split == 'test':
+        key = key.replace('-redyellow', '')
+    return key
+
+
+def read_physion_labels(labels_csv):
+    """{key: 0 | 1} of a Physion labels file (readout_labels.csv / labels.csv): the first column is the key, the column
+    `ground truth outcome` the label (physion.py:325-328)."""
+    import csv
+    with open(labels_csv, newline='') as f:
+        rows = list(csv.reader(f))
+    if not rows or 'ground truth outcome' not in rows[0]:
+        raise ValueError(f"{labels_csv}: no column 'ground truth outcome'")
+    col = rows[0].index('ground truth outcome')
+    out = {}
+    for r in rows[1:]:
+        if not r:
+            continue
+        v = r[col].strip().lower()
+        if v in ('true', '1', '1.0'):
+            out[r[0]] = 1
+        elif v in ('false', '0', '0.0'):
+            out[r[0]] = 0
+        else:
+            raise ValueError(f'{labels_csv}: label {r[col]!r} of {r[0]!r} is neither true nor false')
+    return out
+
+
+class SlotsLabelFileDataModule:
+    """Slots of a file written by unroll.rollout_slots_file / extract.dump_slots with the labels of a Physion CSV as the
+    readout's input (vp_vqa/datasets/physion.py: PhysionSlotsLabelDataset), with SyntheticSlotsLabelDataModule's
+    `train_loader(epoch)` contract: {'slots': [B, video_len, N, D], 'label': [B]}, the videos drawn by a generator
+    seeded per (seed, epoch, rank).  A stored video without a label, or shorter than video_len, raises."""
+
+    def __init__(self, params, slots_path, labels_csv, split='train', steps_per_epoch=8, device='cuda', seed=1234):
+        from .extract import load_slots
+        self.params, self.steps_per_epoch, self.device, self.seed = params, steps_per_epoch, device, seed
+        self.rank = int(os.environ.get('RANK', 0))
+        self.T = params.video_len
+        data = load_slots(slots_path)[split]
+        labels = read_physion_labels(labels_csv)
+        self.files = sorted(data)
+        if not self.files:
+            raise ValueError(f'{slots_path} [{split}]: no videos')
+        self.videos, self.labels = [], []
+        for f in self.files:
+            key = physion_label_key(f, split)
+            if key not in labels:
+                raise KeyError(f'{labels_csv}: no label for {f!r} (key {key!r})')
+            if data[f].shape[0] < self.T:
+                raise ValueError(f'{slots_path} [{split}]: {f!r} has {data[f].shape[0]} frames, video_len is {self.T}')
+            self.videos.append(torch.as_tensor(data[f][:self.T]).float())
+            self.labels.append(float(labels[key]))
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def batches(self, epoch=0):
+        """The video indices of an epoch, [steps][B]: what train_loader stacks."""
+        g = torch.Generator().manual_seed(self.seed + 1000 * epoch + self.rank)
+        return [torch.randint(len(self.videos), (self.params.train_batch_size,), generator=g).tolist()
+                for _ in range(self.steps_per_epoch)]
+
+    def train_loader(self, epoch=0):
+        for vi in self.batches(epoch):
+            yield {'slots': torch.stack([self.videos[v] for v in vi]).to(self.device),
+                   'label': torch.tensor([self.labels[v] for v in vi]).to(self.device)}
 
 
 class SyntheticSlotsLabelDataModule:

@@ -1261,20 +1261,30 @@ class LDMSlotFormer(SADiffusion):
                 r['d_model'] == 256 and r['num_heads'] == 8 and r['history_len'] * r['num_slots'] <= 256 and
                 r['ffn_dim'] % 128 == 0 and r['ffn_dim'] <= 1024)
 
-    def _rollout_slots(self, past, pred_len):
+    def _feed_ok(self):
+        """The inter-step glue as one sdmi_rollout_feed launch: the fused layers, the switch, the kernel's geometry."""
+        r = self.rollout_dict
+        L = r['history_len'] * r['num_slots']
+        Lp = (L + engine.ROLLOUT_TILE - 1) // engine.ROLLOUT_TILE * engine.ROLLOUT_TILE
+        return (self._fused_ok() and kern._ROLLOUT_FEED and r['num_layers'] >= 1 and
+                kern.rollout_feed_covers(r['num_slots'], L, Lp, r['d_model'], r['slot_size']))
+
+    def _rollout_slots(self, past, pred_len, feed=False):
         """past [B, history_len, N, D] fp32 contiguous -> [B, pred_len, N, D] fp32 (slotformer.py:83-126)."""
         r = self.rollout_dict
         grad = self.training and torch.is_grad_enabled()
         fused = not grad and self._fused_ok()
+        feed = feed and fused
         run = lambda x: engine.slot_rollout(self.KG() if grad else self.K(), x, pred_len, r['num_layers'],
-                                            r['num_heads'], fused=fused)
+                                            r['num_heads'], fused=fused, feed=feed)
         if grad:
             return run(past)
         with torch.no_grad():
             if not (fused and self.use_graph):
                 return run(past)
-            # all pred_len steps (7 + 2 num_layers launches each) captured once per (B, pred_len) and replayed
-            key = ('rollout', tuple(past.shape), pred_len)
+            # all pred_len steps (7 + 2 num_layers launches each; feed: 1 + 2 num_layers) captured once per
+            # (B, pred_len) and replayed
+            key = ('unroll' if feed else 'rollout', tuple(past.shape), pred_len)
             g = self._graph_cache.get(key)
             if g is None:
                 sp = torch.empty_like(past)
@@ -1305,6 +1315,17 @@ class LDMSlotFormer(SADiffusion):
         B, T = slots.shape[:2]
         log_dict = self.log_images({'slots': slots.flatten(0, 1)}, use_dpm=True, same_noise=True)
         return {'recon_combined': log_dict['samples'].unflatten(0, (B, T)), 'slots': slots}
+
+    def unroll(self, past_slots, pred_len):
+        """The inference path of rollout() for the rollout stage (slotdiffusion_amd/unroll.py): predicted slots
+        [B, pred_len, N, D] fp32.  bf16 evaluation on the fused layers inside kern.rollout_feed_covers with
+        kern._ROLLOUT_FEED set runs the glue between steps as one sdmi_rollout_feed launch (its own HIP-graph cache
+        key); anything else is exactly rollout()."""
+        if not self._feed_ok():                    # (training mode included: _fused_ok is evaluation only)
+            return self.rollout(past_slots, pred_len)
+        past = past_slots[:, -self.history_len:]
+        assert past.shape[1] == self.history_len, 'wrong burn-in steps'
+        return self._rollout_slots(past.contiguous().float(), pred_len, feed=True)
 
     def forward(self, data_dict):
         """ldm_slotformer.py:159-171."""
