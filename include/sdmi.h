@@ -1086,6 +1086,38 @@ int sdmi_sqerr_rows(const SdmiSqErrArgs* a, void* stream);
  * C2 = (0.03 L)^2.  fp64 arithmetic; out [P] fp64. */
 typedef struct { const float* x; const float* y; double* out; int P, H, W; float data_range; } SdmiSsimArgs;
 int sdmi_ssim(const SdmiSsimArgs* a, void* stream);
+/* Segmentation evaluation, from Slot Attention's attention map straight to contingency tables: replaces, per
+ * frame, the bilinear upsample of the slot masks (img_based/models/sa_diffusion.py:170-180,
+ * video_based/models/savi_diffusion.py:205-214), the argmax over slots (img_based/test_seg.py:27,
+ * video_based/test_seg.py:58), the folding of T into the pixel axis (video_based/test_seg.py:25-30) and the
+ * one_hot products of the metrics (eval_utils.py:161-167, 264-271, 293-301), including the pixel routing of
+ * preproc_masks_overlap (img_based/models/eval_utils.py:119-135).  Frame f of seg [B*T][h*w][N] fp32 (the last
+ * iteration's attention, as sdmi_slot_attention writes it) belongs to sample b at time t:
+ *   time_major = 0:  f = b * T + t   (a batch of clips)       time_major = 1:  f = t * B + b   (the stream's chunks)
+ * Every pixel (y, x) of the H x W output takes pred = argmax over slots (strict >: the lowest index wins a tie)
+ * of the bilinear upsample with align_corners=False, in the arithmetic of sdmi_mask_upsample_argmax expression
+ * for expression (the file is compiled without FMA contraction, like that kernel's), and does
+ *   counts[b][m][row][pred] += 1,   row = Kg where overlap is non-zero at the pixel, else gt_m's id there
+ * for map m = 0 (gt) and, when gt2 is given, m = 1 (gt2); a pixel whose id is outside [0, Kg) and that is not
+ * overlapped is skipped in that map, as in sdmi_contingency.  The extra row Kg keeps the overlapped pixels by
+ * their ORIGINAL predicted id: the host needs that to apply gt -> 0, pred -> pred.max() + 1, whose maximum is
+ * taken before the overwrite (eval_utils.py:131-134).  gt / gt2 / overlap are addressed as
+ *   map[b * map_bstride + t * map_tstride + y * W + x]   (elements),
+ * so a chunk of a [B][Ttotal][H][W] tensor is passed by offsetting the pointer.  `counts` is zeroed by the
+ * caller once per batch of videos; further calls (the next chunk) add to the same tables.  Integer atomics
+ * only: the result does not depend on scheduling.  `ids` (optional) receives the predicted id map
+ * [B*T][H][W] in seg's frame order, int32 (ids_u8 = 0) or uint8 (ids_u8 = 1, N <= 256).
+ * The gate: N >= 1; h, w, H, W >= 1 with any ratio H/h, W/w (integer or not, up- or downsampling);
+ * (Kg + 1) * N <= 8192 per map; the tables plus one source row band must fit 160 KiB of LDS
+ * (SDMI_EUNSUPPORTED otherwise; no shape this project configures is near it). */
+typedef struct {
+  const float* seg; const int* gt; const int* gt2; const int* overlap;
+  int* counts;                           /* [B][maps][Kg + 1][N], maps = 1 + (gt2 != NULL) */
+  void* ids; int ids_u8;
+  int B, T, time_major, N, h, w, H, W, Kg;
+  long long map_bstride, map_tstride;
+} SdmiSegTablesArgs;
+int sdmi_seg_tables(const SdmiSegTablesArgs* a, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

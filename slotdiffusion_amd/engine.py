@@ -265,28 +265,35 @@ def stream_keys_values(model, img):
     return kv.view(T, B, kv.shape[1], kv.shape[2])
 
 
-def stream_recurrence(model, kv, prev_slots=None):
+def stream_recurrence(model, kv, prev_slots=None, want_seg=False):
     """The loop over frames on kv [Tc, B, M, 2 D]: stream_transition + the fused Slot Attention launch per frame (the
-    first frame of a video starts from the learnt init_latents, savi.py:377-380) -> slots [B, Tc, N, D] fp32."""
+    first frame of a video starts from the learnt init_latents, savi.py:377-380) -> slots [B, Tc, N, D] fp32; with
+    want_seg also the last iteration's attention of every frame, time-major [Tc, B, M, N] fp32 (what the evaluation
+    stage turns into segmentation tables: sdmi_seg_tables' time_major order)."""
     K = model.K()
-    out = []
+    out, segs = [], []
     for t in range(kv.shape[0]):
         if prev_slots is None:
             lat = model.init_latents[0]
         else:
             lat = stream_transition(K, prev_slots.contiguous(), model.pred_dict, model.pred_state)
-        prev_slots, _ = K.slot_attention(kv[t], lat, 'slot_attention', model.num_iterations, model.eps)
+        prev_slots, seg = K.slot_attention(kv[t], lat, 'slot_attention', model.num_iterations, model.eps)
         out.append(prev_slots)
+        if want_seg:
+            segs.append(seg)
+    if want_seg:
+        return K.stack_time(out), torch.stack(segs, 0)
     return K.stack_time(out)
 
 
-def encode_stream(model, img, prev_slots=None):
+def encode_stream(model, img, prev_slots=None, want_seg=False):
     """One chunk of a video model's encode for extraction: img [B, Tc, 3, H, W], prev_slots [B, N, D] fp32 (the last
     slots of the chunk before) or None (a new video: the learnt init_latents, and the wrapper's state is cleared,
-    savi.py:453-455) -> slots [B, Tc, N, D] fp32.  stream_keys_values, then stream_recurrence.  Records no gradient."""
+    savi.py:453-455) -> slots [B, Tc, N, D] fp32 (want_seg: and seg [Tc, B, M, N] fp32, see stream_recurrence).
+    stream_keys_values, then stream_recurrence.  Records no gradient."""
     model.pred_state.begin_forward(prev_slots)
     with torch.no_grad():
-        return stream_recurrence(model, stream_keys_values(model, img), prev_slots)
+        return stream_recurrence(model, stream_keys_values(model, img), prev_slots, want_seg)
 
 
 # ------------------------------------------------------------------------------------------

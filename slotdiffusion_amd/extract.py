@@ -76,3 +76,30 @@ class SyntheticVideoDataset:
         g = torch.Generator().manual_seed(self.seed * 100003 + i)
         v = (torch.randn((self.video_len, 3, self.H, self.W), generator=g) * 0.5).clamp_(-1, 1)
         return {'video': v, 'data_idx': i}
+
+
+class SyntheticVideoSegDataset(SyntheticVideoDataset):
+    """SyntheticVideoDataset whose videos also carry ground-truth segmentation, for the evaluation stage
+    (evaluate.evaluate_video_segmentation): 'masks' [T, H, W] int64, id 0 the background and ids 1 .. num_objects
+    rectangles that drift one pixel per frame (later ids cover earlier ones), a function of (seed, i) alone.  The frames
+    are the parent's: the masks are unrelated to them, as random frames are to any scene."""
+
+    def __init__(self, params, num_videos=4, video_len=12, seed=1234, num_objects=4):
+        super().__init__(params, num_videos, video_len, seed)
+        self.num_objects = num_objects
+
+    def get_video(self, i):
+        d = super().get_video(i)
+        g = torch.Generator().manual_seed(self.seed * 7919 + 31 * i + 1)
+        masks = torch.zeros((self.video_len, self.H, self.W), dtype=torch.int64)
+        for k in range(1, self.num_objects + 1):
+            hh = int(torch.randint(max(1, self.H // 8), max(2, self.H // 2), (1,), generator=g))
+            ww = int(torch.randint(max(1, self.W // 8), max(2, self.W // 2), (1,), generator=g))
+            y0 = int(torch.randint(0, self.H - hh + 1, (1,), generator=g))
+            x0 = int(torch.randint(0, self.W - ww + 1, (1,), generator=g))
+            dy, dx = (int(v) for v in torch.randint(-1, 2, (2,), generator=g))
+            for t in range(self.video_len):
+                y, x = (y0 + dy * t) % self.H, (x0 + dx * t) % self.W
+                masks[t, y:y + hh, x:x + ww] = k
+        d['masks'] = masks
+        return d

@@ -7,6 +7,11 @@ error -- runs in HIP kernels (sdmi_contingency, sdmi_sqerr_rows); what is left i
 [B, C, K] table of exact integers, done with the reference's own float32 formulas on the host, and
 scipy's linear_sum_assignment for the matching, exactly as the reference does.
 
+The evaluation stage (slotdiffusion_amd/evaluate.py) does not make id maps at all: sdmi_seg_tables turns Slot
+Attention's attention map into the tables directly (seg_tables), with one extra row for the pixels of the overlap
+map of COCO / VOC (img_based/models/eval_utils.py:119-135), and scores_from_tables does the arithmetic.  The five
+*_metric functions take the reference's optional third argument, inst_overlap_mask, through the same tables.
+
 Not covered: SSIM / LPIPS (skimage / lpips networks), bounding-box AP/AR (torchvision ops),
 postproc_mask.
 """
@@ -16,7 +21,8 @@ import torch
 from . import _lib
 
 __all__ = ['contingency', 'adjusted_rand_index', 'ARI_metric', 'fARI_metric', 'miou_metric',
-           'fmiou_metric', 'mbo_metric', 'mse_metric', 'psnr_metric']
+           'fmiou_metric', 'mbo_metric', 'mse_metric', 'psnr_metric', 'seg_tables', 'seg_tables_covers',
+           'overlap_tables', 'scores_from_tables', 'batch_scores']
 
 
 def _need_gpu(t):
@@ -66,18 +72,25 @@ def adjusted_rand_index(true_ids, pred_ids, ignore_background=False):
     return _ari_from_table(N)
 
 
-def ARI_metric(x, y):
+def ARI_metric(x, y, inst_overlap_mask=None):
+    if inst_overlap_mask is not None:
+        return batch_scores(overlap_tables(x, y, inst_overlap_mask), ('ari',))['ari']
     return adjusted_rand_index(x, y, ignore_background=False).mean().item()
 
 
-def fARI_metric(x, y):
+def fARI_metric(x, y, inst_overlap_mask=None):
+    if inst_overlap_mask is not None:
+        return batch_scores(overlap_tables(x, y, inst_overlap_mask), ('fari',))['fari']
     return adjusted_rand_index(x, y, ignore_background=True).mean().item()
 
 
 def _iou_tables(gt_mask, pred_mask):
     """Per-image (intersect [N_i, M_i] float32) with the per-image one_hot widths of the
     reference (N_i = max gt id of the image + 1, M_i likewise)."""
-    T = contingency(gt_mask, pred_mask).cpu()
+    return _crop_per_image(contingency(gt_mask, pred_mask).cpu())
+
+
+def _crop_per_image(T):
     out = []
     for b in range(T.shape[0]):
         t = T[b]
@@ -110,18 +123,23 @@ def _hungarian_miou(inter, ignore_background):
     return iou[row_ind, col_ind].sum() / float(N)
 
 
-def miou_metric(gt_mask, pred_mask, ignore_background=False):
+def miou_metric(gt_mask, pred_mask, inst_overlap_mask=None, ignore_background=False):
+    if inst_overlap_mask is not None:
+        k = 'fmiou' if ignore_background else 'miou'
+        return batch_scores(overlap_tables(gt_mask, pred_mask, inst_overlap_mask), (k,))[k]
     ious = [_hungarian_miou(t, ignore_background) for t in _iou_tables(gt_mask, pred_mask)]
     if all(np.isnan(v) for v in ious):
         return np.nan
     return np.nanmean(ious)
 
 
-def fmiou_metric(gt_mask, pred_mask):
-    return miou_metric(gt_mask, pred_mask, ignore_background=True)
+def fmiou_metric(gt_mask, pred_mask, inst_overlap_mask=None):
+    return miou_metric(gt_mask, pred_mask, inst_overlap_mask, ignore_background=True)
 
 
-def mbo_metric(gt_mask, pred_mask):
+def mbo_metric(gt_mask, pred_mask, inst_overlap_mask=None):
+    if inst_overlap_mask is not None:
+        return batch_scores(overlap_tables(gt_mask, pred_mask, inst_overlap_mask), ('mbo',))['mbo']
     mbos = []
     for t in _iou_tables(gt_mask, pred_mask):
         if t.shape[0] == 1:
@@ -129,6 +147,138 @@ def mbo_metric(gt_mask, pred_mask):
         else:
             mbos.append(_iou(t, True).max(1).mean())
     return np.nanmean(mbos)
+
+
+# ------------------------------------------------------------------------------------------
+# tables with the overlap row (sdmi_seg_tables' layout) and the scores on them
+# ------------------------------------------------------------------------------------------
+SCORE_KEYS = ('ari', 'fari', 'miou', 'fmiou', 'mbo')
+_SEG_LDS = 160 * 1024
+
+
+def seg_tables_covers(N, Kg, w, maps=1):
+    """The gate of sdmi_seg_tables (include/sdmi.h): the table size sdmi_contingency admits, and the tables plus a
+    one-row band (two source rows) inside the LDS."""
+    if not (N >= 1 and Kg >= 1 and w >= 1 and (Kg + 1) * N <= 8192):
+        return False
+    return maps * (Kg + 1) * N * 4 + ((2 * w * N + 11) // 4 * 4) * 4 <= _SEG_LDS
+
+
+def seg_tables(seg, gt, hw, num_true, *, time_major=False, gt2=None, overlap=None, counts=None, ids_dtype=None,
+               fused=None):
+    """Slot Attention's attention map -> contingency tables, without masks or id maps in memory (sdmi_seg_tables).
+
+    seg [F, h*w, N] fp32 with hw = (h, w), F = B * T frames in [B][T] order (time_major=False) or the stream's [T][B]
+    order (True).  gt, gt2 (optional second ground truth: semantic ids), overlap (optional; non-zero = overlapped):
+    int32 [B, T, H, W], any batch / time strides (a chunk of a longer video is a plain slice).  num_true = Kg.
+    -> counts int32 [B, maps, Kg + 1, N] (row Kg: the overlapped pixels by predicted id), created zeroed when not
+    given and otherwise ADDED to (the next chunk of the same videos), and the id map [F, H, W] when ids_dtype
+    (torch.int32 / torch.uint8) asks for one.  Outside seg_tables_covers, or with fused=False, the same tables come
+    from the composed path: mask_upsample_argmax(want_up=False), then sdmi_contingency on rows remapped by `overlap`."""
+    from . import ops
+    _need_gpu(seg)
+    h, w = hw
+    F_, M, N = seg.shape
+    B, T, H, W = gt.shape
+    Kg = int(num_true)
+    maps_in = [gt] + ([gt2] if gt2 is not None else [])
+    assert F_ == B * T and M == h * w and seg.dtype == torch.float32
+    for m in maps_in + ([overlap] if overlap is not None else []):
+        _need_gpu(m)
+        assert m.dtype == torch.int32 and m.shape == gt.shape and m.stride() == gt.stride(), 'maps share shape and strides'
+    assert gt.stride(3) == 1 and gt.stride(2) == W, 'a map\'s [H, W] plane is contiguous'
+    if counts is None:
+        counts = torch.zeros((B, len(maps_in), Kg + 1, N), dtype=torch.int32, device=seg.device)
+    assert counts.shape == (B, len(maps_in), Kg + 1, N) and counts.dtype == torch.int32 and counts.is_contiguous()
+    seg = seg.contiguous()
+    if seg.data_ptr() % 16:
+        seg = seg.clone()
+    if fused is None:
+        fused = seg_tables_covers(N, Kg, w, len(maps_in))
+    if fused:
+        ids = torch.empty((F_, H, W), dtype=ids_dtype, device=seg.device) if ids_dtype is not None else None
+        assert ids_dtype in (None, torch.int32, torch.uint8)
+        _lib.call('sdmi_seg_tables', torch.cuda.current_stream().cuda_stream, seg=seg.data_ptr(), gt=gt.data_ptr(),
+                  gt2=gt2.data_ptr() if gt2 is not None else 0, overlap=overlap.data_ptr() if overlap is not None else 0,
+                  counts=counts.data_ptr(), ids=ids.data_ptr() if ids is not None else 0,
+                  ids_u8=int(ids_dtype == torch.uint8), B=B, T=T, time_major=int(time_major), N=N, h=h, w=w, H=H, W=W,
+                  Kg=Kg, map_bstride=gt.stride(0), map_tstride=gt.stride(1))
+        return (counts, ids) if ids_dtype is not None else counts
+    _, idx = ops.mask_upsample_argmax(seg, h, w, H, W, want_up=False)           # [F, H, W] int64
+    idx = idx.view(T, B, H, W).transpose(0, 1) if time_major else idx.view(B, T, H, W)
+    for i, m in enumerate(maps_in):
+        rows = m if overlap is None else torch.where(overlap != 0, torch.full_like(m, Kg), m)
+        counts[:, i] += contingency(rows, idx, Kg + 1, N)
+    if ids_dtype is not None:
+        flat = idx.transpose(0, 1) if time_major else idx
+        return counts, flat.reshape(F_, H, W).to(ids_dtype)
+    return counts
+
+
+def overlap_tables(gt_mask, pred_mask, inst_overlap_mask=None):
+    """Id maps [B, ...] (+ overlap map of the same shape, non-zero = overlapped) -> int table [B, Kg + 1, N] on the CPU in
+    sdmi_seg_tables' layout: overlapped pixels are counted in the extra row Kg under their predicted id."""
+    Kg, N = int(gt_mask.max()) + 1, int(pred_mask.max()) + 1
+    rows = gt_mask
+    if inst_overlap_mask is not None:
+        rows = torch.where(inst_overlap_mask.to(gt_mask.device) != 0, torch.full_like(gt_mask, Kg), gt_mask)
+    return contingency(rows, pred_mask, Kg + 1, N).cpu()
+
+
+def _resolve_overlap(tab):
+    """One sample's [Kg + 1, N] integer table -> [Kg, N + 1]: the reference's preproc_masks_overlap on counts
+    (img_based/models/eval_utils.py:130-134).  The overlapped pixels (row Kg) become gt 0 / predicted id
+    `largest predicted id of the image + 1`, that maximum taken over ALL pixels, overlapped ones included."""
+    body, extra = tab[:-1], tab[-1]
+    out = torch.zeros((body.shape[0], body.shape[1] + 1), dtype=tab.dtype)
+    out[:, :-1] = body
+    n_ov = int(extra.sum())
+    if n_ov:
+        top = int(torch.nonzero(body.sum(0) + extra).max())
+        out[0, top + 1] += n_ov
+    return out
+
+
+def scores_from_tables(tables, keys=SCORE_KEYS):
+    """tables: integer [S, Kg + 1, N] (sdmi_seg_tables' / overlap_tables' layout; any device) of ONE batch, in the sense
+    of the reference's metric functions: the S samples share the one_hot widths of adjusted_rand_index
+    (eval_utils.py:161-167).  -> {key: float array [S]} per-sample ARI, FG-ARI (float32, reference operation order:
+    _ari_from_table), Hungarian mIoU, foreground mIoU and mBO (NaN where the reference returns NaN: a ground truth
+    that holds the background id alone)."""
+    tabs = torch.stack([_resolve_overlap(t) for t in torch.as_tensor(tables).cpu().long()])      # [S, Kg, N + 1]
+    out = {}
+    if 'ari' in keys or 'fari' in keys:
+        used_r = torch.nonzero(tabs.sum((0, 2))).flatten()
+        used_c = torch.nonzero(tabs.sum((0, 1))).flatten()
+        C = int(used_r.max()) + 1 if len(used_r) else 1
+        K = int(used_c.max()) + 1 if len(used_c) else 1
+        full = tabs[:, :C, :K].float().contiguous()
+        if 'ari' in keys:
+            out['ari'] = _ari_from_table(full).numpy()
+        if 'fari' in keys:
+            out['fari'] = _ari_from_table(full[:, 1:].contiguous()).numpy()
+    per = _crop_per_image(tabs)
+    if 'miou' in keys:
+        out['miou'] = np.array([_hungarian_miou(t, False) for t in per], dtype=np.float64)
+    if 'fmiou' in keys:
+        out['fmiou'] = np.array([_hungarian_miou(t, True) for t in per], dtype=np.float64)
+    if 'mbo' in keys:
+        out['mbo'] = np.array([np.nan if t.shape[0] == 1 else _iou(t, True).max(1).mean() for t in per], dtype=np.float64)
+    return out
+
+
+def batch_scores(tables, keys=SCORE_KEYS, per_sample=None):
+    """The reference's value of each metric for one batch (eval_utils.py:190-211, 310-370): the float32 mean of the
+    per-sample ARI / FG-ARI, the nanmean of the others (NaN when every sample is NaN)."""
+    per = per_sample if per_sample is not None else scores_from_tables(tables, keys)
+    out = {}
+    for k in keys:
+        v = per[k]
+        if k in ('ari', 'fari'):
+            out[k] = torch.from_numpy(np.asarray(v, dtype=np.float32)).mean().item()
+        else:
+            out[k] = np.nan if np.all(np.isnan(v)) else float(np.nanmean(v))
+    return out
 
 
 def _sqerr(x, y, mode=0):

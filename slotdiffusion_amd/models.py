@@ -875,9 +875,10 @@ class SAViDiffusion(SADiffusion):
         return _encode_clip(self, img, prev_slots)
 
     @torch.no_grad()
-    def encode_stream(self, img, prev_slots=None):
-        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]."""
-        return engine.encode_stream(self, img, prev_slots)
+    def encode_stream(self, img, prev_slots=None, want_seg=False):
+        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]; want_seg: and the
+        attention maps [Tc,B,h*w,N] the segmentation evaluation reads."""
+        return engine.encode_stream(self, img, prev_slots, want_seg)
 
     def calc_train_loss(self, data_dict, out_dict):
         """savi_diffusion.py:252-264: the LDM sees the B*T frames as independent images."""
@@ -1016,9 +1017,10 @@ class SAVi(SA):
         return _encode_clip(self, img, prev_slots)[0]
 
     @torch.no_grad()
-    def encode_stream(self, img, prev_slots=None):
-        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]."""
-        return engine.encode_stream(self, img, prev_slots)
+    def encode_stream(self, img, prev_slots=None, want_seg=False):
+        """One chunk of a long video for slot extraction (engine.encode_stream) -> slots [B,Tc,N,D]; want_seg: and the
+        attention maps [Tc,B,h*w,N] the segmentation evaluation reads."""
+        return engine.encode_stream(self, img, prev_slots, want_seg)
 
     def forward(self, data_dict):
         """savi.py:445-475 (clips longer than clip_len are not split: 288 GB of HBM)."""

@@ -1,4 +1,5 @@
 """Registry module with the surface of `slotdiffusion.video_based` (scripts/train.py:97-100)."""
+from ..evaluate import evaluate_video_segmentation  # noqa: F401
 from ..extract import extract_video_slots  # noqa: F401
 from ..method import SyntheticDataModule, build_method  # noqa: F401
 from ..models import build_model  # noqa: F401
