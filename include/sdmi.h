@@ -198,6 +198,16 @@ enum {
   SDMI_WGRAD_KERNEL_F32_T64 = 4      /* exact fp32, 64 x 64 tiles */
 };
 int sdmi_wgrad_kernel(const SdmiWgradArgs* a, void* stream);
+/* Host-side query, no launch (pointers are not read; same argument checks, negative on failure): the full kernel
+ * instantiation sdmi_wgrad dispatches for these arguments, from the same selection the launcher itself uses, so that a
+ * test can assert which kernel serves a case.  Packed as
+ *   bits  0.. 3  family (SDMI_WGRAD_KERNEL_*: what sdmi_wgrad_kernel returns)
+ *   bits  4.. 6  TN / 64        bits 7.. 9  TK / 64     (output tile of wgrad_tr_kernel<TN, TK, MODE> and of the fp32
+ *                                                        wgrad_kernel<float, TN, TK, IS1X1>; 0 for the direct kernels)
+ *   bits 10..11  IGEMM: loader MODE (0 general gather, 1 1x1 / linear, 2 stride-1 same-size convolution);
+ *                F32_*: IS1X1;  0 for the direct kernels
+ *   bits 12..14  HALO: LOGW (4, 5, 6);  0 otherwise */
+int sdmi_wgrad_route(const SdmiWgradArgs* a, void* stream);
 /* Fold the split partials of up to 16 earlier sdmi_wgrad(defer_fold = 1) launches into their dw / dbias
  * (+= when accumulate) in ONE launch.  `problems` (see SdmiWgradGroupArgs below) is a HOST array of the
  * same SdmiWgradArgs (dw, dbias, workspace, N, K, splits, accumulate are read); destinations must be
@@ -241,6 +251,14 @@ typedef struct {
   int dgrad_cap, wgrad_tile;
 } SdmiBwdPairArgs;
 int sdmi_bwd_pair(const SdmiBwdPairArgs* a, void* stream);
+/* Host-side query, no launch: the bwd_pair_kernel<BM, BN, BKB, MODE, WT> sdmi_bwd_pair launches for these arguments.
+ * It runs sdmi_bwd_pair's own argument checks (non-null, 16-byte aligned operand pointers included; nothing is
+ * dereferenced on the device) and fails as it does; the launcher takes the same decision function's answer.  Packed as
+ *   bits 0.. 2  BM / 64     bits 3.. 5  BN / 64     (data-gradient tile)
+ *   bits 6.. 8  BKB / 64    (data-gradient K tile bytes)
+ *   bits 9..10  MODE (1 1x1 / linear, 2 stride-1 convolution)
+ *   bits 12..14 WT / 64     (weight-gradient tile) */
+int sdmi_bwd_pair_route(const SdmiBwdPairArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GroupNorm (+ fused activation) on NHWC, statistics in fp32.

@@ -103,38 +103,48 @@ int launch_pair(const SdmiGemmArgs& d, const SdmiWgradArgs& w, const SdmiWgradAr
   return sdmi_check_launch("bwd_pair");
 }
 
-}  // namespace
+// The instantiation bwd_pair_kernel<BM, BN, BKB, MODE, WT> an argument set takes, decided HERE alone: sdmi_bwd_pair
+// launches what this answers and sdmi_bwd_pair_route reports it, so query and launch cannot disagree.
+struct PairRoute { int bm, bn, bkb, mode, wt, hw_shift; };
 
-extern "C" int sdmi_bwd_pair(const SdmiBwdPairArgs* a, void* stream) {
-  SDMI_REQUIRE(a && a->dgrad && a->wgrad, "null pointer");
+// every argument check of sdmi_bwd_pair, then the decision (`who`: the entry point the error message names)
+#define PAIR_REQUIRE(cond, msg)              \
+  do {                                       \
+    if (!(cond)) {                           \
+      sdmi_set_error("%s: %s", who, msg);    \
+      return SDMI_EINVAL;                    \
+    }                                        \
+  } while (0)
+int pair_route(const SdmiBwdPairArgs* a, PairRoute& route, const char* who) {
+  PAIR_REQUIRE(a && a->dgrad && a->wgrad, "null pointer");
   const SdmiGemmArgs& d = *(const SdmiGemmArgs*)a->dgrad;
   const SdmiWgradArgs& w = *(const SdmiWgradArgs*)a->wgrad;
   const SdmiWgradArgs* f = (const SdmiWgradArgs*)a->fold;
-  SDMI_REQUIRE(d.a && d.w && d.out && w.a && w.dy && w.dw, "null operand");
-  SDMI_REQUIRE(d.dtype == SDMI_BF16 && d.out_dtype == SDMI_BF16 && w.dtype == SDMI_BF16, "bf16 operands only");
+  PAIR_REQUIRE(d.a && d.w && d.out && w.a && w.dy && w.dw, "null operand");
+  PAIR_REQUIRE(d.dtype == SDMI_BF16 && d.out_dtype == SDMI_BF16 && w.dtype == SDMI_BF16, "bf16 operands only");
   // ---- the data gradient: a 1x1 / linear problem or a plain stride-1 convolution over dY
   const bool d1x1 = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_t == 0 && d.pad_l == 0 && !d.ups && d.zins <= 1;
   const bool dplain = !d1x1 && !d.ups && d.zins <= 1 && d.stride == 1;
-  SDMI_REQUIRE(d1x1 || dplain, "data gradient: 1x1 or plain stride-1 convolution");
-  SDMI_REQUIRE(d.M > 0 && d.N > 64 && d.K > 0 && d.K == d.KH * d.KW * d.Cin && d.M == d.B * d.Ho * d.Wo, "bad dgrad geometry");
-  SDMI_REQUIRE(d.Cin % 8 == 0 && d.lda % 8 == 0 && d.ldw % 8 == 0 && ((uintptr_t)d.a & 15) == 0 && ((uintptr_t)d.w & 15) == 0,
+  PAIR_REQUIRE(d1x1 || dplain, "data gradient: 1x1 or plain stride-1 convolution");
+  PAIR_REQUIRE(d.M > 0 && d.N > 64 && d.K > 0 && d.K == d.KH * d.KW * d.Cin && d.M == d.B * d.Ho * d.Wo, "bad dgrad geometry");
+  PAIR_REQUIRE(d.Cin % 8 == 0 && d.lda % 8 == 0 && d.ldw % 8 == 0 && ((uintptr_t)d.a & 15) == 0 && ((uintptr_t)d.w & 15) == 0,
                "dgrad operands must keep 16-byte vectors");
-  SDMI_REQUIRE(!d.a2 && !d.ln_colsum && !d.geglu && !d.softmax8 && !d.out2 && d.osy == 0 && !(d.batch > 1) && !d.rowvec &&
+  PAIR_REQUIRE(!d.a2 && !d.ln_colsum && !d.geglu && !d.softmax8 && !d.out2 && d.osy == 0 && !(d.batch > 1) && !d.rowvec &&
                !d.bias_m && d.split_k <= 1, "data gradient: plain epilogue (alpha, bias, residual) only");
   const long long a_bytes = ((long long)d.B * d.H * d.W + (long long)(d.KH + 1) * d.W) * d.lda * 2;
-  SDMI_REQUIRE(a_bytes < (1ll << 31) && (long long)d.N * d.ldw * 2 < (1ll << 31), "dgrad operands beyond 31-bit offsets");
+  PAIR_REQUIRE(a_bytes < (1ll << 31) && (long long)d.N * d.ldw * 2 < (1ll << 31), "dgrad operands beyond 31-bit offsets");
   // ---- the weight gradient: 128 x 128 output tiles, same loader class as the data gradient
   const bool w1x1 = w.KH == 1 && w.KW == 1 && w.stride == 1 && w.pad_t == 0 && w.pad_l == 0 && !w.ups && w.H == w.Ho &&
                     w.W == w.Wo;
   const bool wlin = !w1x1 && !w.ups && w.stride == 1 && w.H == w.Ho && w.W == w.Wo;
-  SDMI_REQUIRE((d1x1 && w1x1) || (dplain && wlin), "both gradients must be 1x1, or both a stride-1 same-size convolution");
-  SDMI_REQUIRE(w.N > 64 && w.K > 64 && w.K == w.KH * w.KW * w.Cin && w.M == w.B * w.Ho * w.Wo && w.Cin % 8 == 0 &&
+  PAIR_REQUIRE((d1x1 && w1x1) || (dplain && wlin), "both gradients must be 1x1, or both a stride-1 same-size convolution");
+  PAIR_REQUIRE(w.N > 64 && w.K > 64 && w.K == w.KH * w.KW * w.Cin && w.M == w.B * w.Ho * w.Wo && w.Cin % 8 == 0 &&
                w.lda % 8 == 0 && w.ldy % 8 == 0, "bad wgrad geometry");
-  SDMI_REQUIRE(w.splits >= 1 && (w.splits == 1 || w.workspace), "splits > 1 need a workspace");
+  PAIR_REQUIRE(w.splits >= 1 && (w.splits == 1 || w.workspace), "splits > 1 need a workspace");
   const long long mps = ((long long)w.M + w.splits - 1) / w.splits + 64;
   const long long ld = w.lda > w.ldy ? w.lda : w.ldy;
-  SDMI_REQUIRE((mps + (long long)(w.KH + 1) * w.W + 64) * ld * 2 < (1ll << 31), "wgrad split beyond 31-bit offsets");
-  if (f) SDMI_REQUIRE(f->dw && f->workspace && f->splits > 1 && f->N > 0 && f->K > 0 && ((long long)f->N * f->K) % 4 == 0 &&
+  PAIR_REQUIRE((mps + (long long)(w.KH + 1) * w.W + 64) * ld * 2 < (1ll << 31), "wgrad split beyond 31-bit offsets");
+  if (f) PAIR_REQUIRE(f->dw && f->workspace && f->splits > 1 && f->N > 0 && f->K > 0 && ((long long)f->N * f->K) % 4 == 0 &&
                       f->dw != w.dw && (!f->dbias || f->dbias != w.dbias), "bad fold problem (or it targets this layer's dW)");
   int hw_shift = -1;
   {
@@ -152,22 +162,42 @@ extern "C" int sdmi_bwd_pair(const SdmiBwdPairArgs* a, void* stream) {
   if (d1x1 && kbytes <= 512) big = false;
   const bool wide = kbytes >= 512;
   const int bk = (wide ? 128 : 64) / 2;
-  if (!d1x1) SDMI_REQUIRE(d.KH * d.KW <= 32 && d.Cin % bk == 0, "convolution data gradient: K tiles must lie inside one filter tap");
-  hipStream_t st = (hipStream_t)stream;
-  SDMI_REQUIRE(a->wgrad_tile == 0 || a->wgrad_tile == 128 || (a->wgrad_tile == 64 && !big),
+  if (!d1x1) PAIR_REQUIRE(d.KH * d.KW <= 32 && d.Cin % bk == 0, "convolution data gradient: K tiles must lie inside one filter tap");
+  PAIR_REQUIRE(a->wgrad_tile == 0 || a->wgrad_tile == 128 || (a->wgrad_tile == 64 && !big),
                "wgrad_tile: 128, or 64 next to 64 x 64 data-gradient tiles");
+  const int t = big ? 128 : 64;
+  route = {t, t, wide ? 128 : 64, d1x1 ? 1 : 2, a->wgrad_tile == 64 ? 64 : 128, hw_shift};
+  return 0;
+}
+#undef PAIR_REQUIRE
+
+}  // namespace
+
+extern "C" int sdmi_bwd_pair(const SdmiBwdPairArgs* a, void* stream) {
+  PairRoute r;
+  if (const int rc = pair_route(a, r, __func__)) return rc;
+  const SdmiGemmArgs& d = *(const SdmiGemmArgs*)a->dgrad;
+  const SdmiWgradArgs& w = *(const SdmiWgradArgs*)a->wgrad;
+  const SdmiWgradArgs* f = (const SdmiWgradArgs*)a->fold;
+  hipStream_t st = (hipStream_t)stream;
 #define PAIR_GO(BM, BN, BKB, WT)                                                                       \
-  return d1x1 ? launch_pair<BM, BN, BKB, 1, WT>(d, w, f, a->dgrad_cap, hw_shift, st)                    \
-              : launch_pair<BM, BN, BKB, 2, WT>(d, w, f, a->dgrad_cap, hw_shift, st)
-  if (big) {
-    if (wide) PAIR_GO(128, 128, 128, 128);
+  return r.mode == 1 ? launch_pair<BM, BN, BKB, 1, WT>(d, w, f, a->dgrad_cap, r.hw_shift, st)           \
+                     : launch_pair<BM, BN, BKB, 2, WT>(d, w, f, a->dgrad_cap, r.hw_shift, st)
+  if (r.bm == 128) {
+    if (r.bkb == 128) PAIR_GO(128, 128, 128, 128);
     PAIR_GO(128, 128, 64, 128);
   }
-  if (a->wgrad_tile == 64) {
-    if (wide) PAIR_GO(64, 64, 128, 64);
+  if (r.wt == 64) {
+    if (r.bkb == 128) PAIR_GO(64, 64, 128, 64);
     PAIR_GO(64, 64, 64, 64);
   }
-  if (wide) PAIR_GO(64, 64, 128, 128);
+  if (r.bkb == 128) PAIR_GO(64, 64, 128, 128);
   PAIR_GO(64, 64, 64, 128);
 #undef PAIR_GO
+}
+
+extern "C" int sdmi_bwd_pair_route(const SdmiBwdPairArgs* a, void*) {
+  PairRoute r;
+  if (const int rc = pair_route(a, r, __func__)) return rc;
+  return (r.bm / 64) | (r.bn / 64) << 3 | (r.bkb / 64) << 6 | r.mode << 9 | (r.wt / 64) << 12;
 }

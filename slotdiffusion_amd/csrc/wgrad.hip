@@ -563,6 +563,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_c64_kernel(SdmiWgradArgs p) {
         }
     }
   }
+  if (!p.dbias) return;                              // (the bias partials of the workspace stay untouched)
   __syncthreads();
   float* red = reinterpret_cast<float*>(smem);       // [256][8]
 #pragma unroll
@@ -606,7 +607,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(SdmiWgradArgs p, int
   const int tiles_y = p.H / TH;
   const int n_tiles = p.B * tiles_y;
   const int split = blockIdx.x, nsplit = gridDim.x;
-  const bool want_bias = cb == 0;
+  const bool want_bias = cb == 0 && p.dbias;      // (no dbias: the bias partials of the workspace stay untouched)
 
   u32x4 prex[HV], prey[DV];
   float bsum[8];
@@ -763,32 +764,41 @@ static bool wgrad_is1x1(const SdmiWgradArgs& a) {
 }
 
 // Which kernel a problem takes is decided by the two select_* functions alone: the dispatchers below launch what they
-// answer and sdmi_wgrad_kernel reports it, so query and launch cannot disagree.
-int select_wgrad_f32(const SdmiWgradArgs& a) {
+// answer and sdmi_wgrad_kernel / sdmi_wgrad_route report it, so query and launch cannot disagree.  The answer names the
+// full instantiation: the family, and what that family is templated on (0 where it has no such parameter).
+struct WgradRoute {
+  int family;       // SDMI_WGRAD_KERNEL_*
+  int tn, tk;       // output tile: wgrad_tr_kernel<TN, TK, MODE> / wgrad_kernel<float, TN, TK, IS1X1>
+  int mode;         // wgrad_tr_kernel: loader MODE 0 / 1 / 2;  wgrad_kernel<float>: IS1X1
+  int logw;         // wgrad3x3_halo_kernel<LOGW>
+};
+
+WgradRoute select_wgrad_f32(const SdmiWgradArgs& a) {
   // exact-fp32 MFMA runs at 1/16 of the bf16 rate (0.6 TFLOP/s per CU), so a launch with few workgroups is
   // COMPUTE bound on the handful of CUs it occupies: the Slot Attention / predictor layers (M = clips x slots
   // = 240 ... 448 rows, N, K <= 768) gave 4 - 36 workgroups of 128 x 128 and took 34 - 50 us each.  Below 96
   // workgroups the 64 x 64 tiles (four times the workgroups, a quarter of the work each) are used.
   const long long wg128 = (long long)((a.N + 127) / 128) * ((a.K + 127) / 128) * a.splits;
   const bool small = a.N <= 64 || a.K <= 64 || wg128 < 96;
-  return small ? SDMI_WGRAD_KERNEL_F32_T64 : SDMI_WGRAD_KERNEL_F32_T128;
+  const int t = small ? 64 : 128;
+  return {small ? SDMI_WGRAD_KERNEL_F32_T64 : SDMI_WGRAD_KERNEL_F32_T128, t, t, wgrad_is1x1(a) ? 1 : 0, 0};
 }
 
 int dispatch_wgrad_f32(const SdmiWgradArgs& a, hipStream_t st) {
-  const bool is1x1 = wgrad_is1x1(a);
-  if (select_wgrad_f32(a) == SDMI_WGRAD_KERNEL_F32_T64)
-    return is1x1 ? launch_wgrad<float, 64, 64, true>(a, st)
-                 : launch_wgrad<float, 64, 64, false>(a, st);
-  return is1x1 ? launch_wgrad<float, 128, 128, true>(a, st)
-               : launch_wgrad<float, 128, 128, false>(a, st);
+  const WgradRoute r = select_wgrad_f32(a);
+  if (r.tn == 64)
+    return r.mode ? launch_wgrad<float, 64, 64, true>(a, st)
+                  : launch_wgrad<float, 64, 64, false>(a, st);
+  return r.mode ? launch_wgrad<float, 128, 128, true>(a, st)
+                : launch_wgrad<float, 128, 128, false>(a, st);
 }
 
-int select_wgrad_bf16(const SdmiWgradArgs& a) {
+WgradRoute select_wgrad_bf16(const SdmiWgradArgs& a) {
   // direct kernel for the 64 -> 64 channel 3x3 layers at full resolution (one workgroup per M-split slot)
   if (a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_t == 1 && a.pad_l == 1 && !a.ups && a.Cin == 64 &&
       a.N == 64 && a.K == 576 && a.H == a.Ho && a.W == a.Wo && a.W % 64 == 0 && a.H % 4 == 0 && a.splits >= 2 &&
       (long long)a.B * (a.H / 4) * (a.W / 64) >= a.splits && (long long)a.B * a.H * a.W * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
-    return SDMI_WGRAD_KERNEL_C64;
+    return {SDMI_WGRAD_KERNEL_C64, 0, 0, 0, 0};
   // ... and for every other 3x3 stride-1 layer on 16 / 32 / 64-column power-of-two images (pairs of 64 output x 64
   // input channels; the caller sizes `splits` so that pairs x splits fills the chip: bwd.py).  The kernel always
   // writes M-split partials for the fold behind it, so -- like the 64-channel kernel above -- it takes splits >= 2 only:
@@ -804,28 +814,29 @@ int select_wgrad_bf16(const SdmiWgradArgs& a) {
       a.W == a.Wo && a.Cin % 64 == 0 && a.N % 64 == 0 && a.K == 9 * a.Cin && hw % 256 == 0 && (hw & (hw - 1)) == 0 &&
       a.splits >= 2 && a.M / 256 >= a.splits && (a.N / 64) * (a.Cin / 64) * a.splits >= 128 &&
       (long long)a.M * (a.lda > a.ldy ? a.lda : a.ldy) < (1ll << 40))
-    return SDMI_WGRAD_KERNEL_HALO;
-  return SDMI_WGRAD_KERNEL_IGEMM;
-}
-
-int dispatch_wgrad_bf16(const SdmiWgradArgs& a, hipStream_t st) {
-  const int which = select_wgrad_bf16(a);
-  if (which == SDMI_WGRAD_KERNEL_C64) return launch_wgrad3x3_c64(a, st);
-  if (which == SDMI_WGRAD_KERNEL_HALO)
-    return a.W == 16 ? launch_wgrad3x3_halo<4>(a, st) : (a.W == 32 ? launch_wgrad3x3_halo<5>(a, st) : launch_wgrad3x3_halo<6>(a, st));
+    return {SDMI_WGRAD_KERNEL_HALO, 0, 0, 0, logw};
+  // the implicit GEMM: 64-wide tiles for N, K <= 64; the loader MODE of wgrad_body.h
   const bool is1x1 = wgrad_is1x1(a);
-  const bool n64 = a.N <= 64, k64 = a.K <= 64;
-  // "same" stride-1 convolution on a power-of-two image: the input pixel is linear in m
+  // "same" stride-1 convolution: the input pixel is linear in m
   const bool lin = !is1x1 && !a.ups && a.stride == 1 && a.H == a.Ho && a.W == a.Wo;
   // the scalar-only loaders address a split's rows with 31-bit byte offsets
   const long long mps = ((long long)a.M + a.splits - 1) / a.splits + 64;
   const long long ld = a.lda > a.ldy ? a.lda : a.ldy;
   const bool fits = (mps + (long long)(a.KH + 1) * a.W + 64) * ld * 2 < (1ll << 31);
+  return {SDMI_WGRAD_KERNEL_IGEMM, a.N <= 64 ? 64 : 128, a.K <= 64 ? 64 : 128,
+          is1x1 && fits ? 1 : (lin && fits ? 2 : 0), 0};
+}
+
+int dispatch_wgrad_bf16(const SdmiWgradArgs& a, hipStream_t st) {
+  const WgradRoute r = select_wgrad_bf16(a);
+  if (r.family == SDMI_WGRAD_KERNEL_C64) return launch_wgrad3x3_c64(a, st);
+  if (r.family == SDMI_WGRAD_KERNEL_HALO)
+    return r.logw == 4 ? launch_wgrad3x3_halo<4>(a, st) : (r.logw == 5 ? launch_wgrad3x3_halo<5>(a, st) : launch_wgrad3x3_halo<6>(a, st));
 #define WG_TR(TN, TK)                                                              \
-  (is1x1 && fits ? launch_wgrad_tr<TN, TK, 1>(a, st)                               \
-   : lin && fits ? launch_wgrad_tr<TN, TK, 2>(a, st) : launch_wgrad_tr<TN, TK, 0>(a, st))
-  if (n64) return k64 ? WG_TR(64, 64) : WG_TR(64, 128);
-  return k64 ? WG_TR(128, 64) : WG_TR(128, 128);
+  (r.mode == 1   ? launch_wgrad_tr<TN, TK, 1>(a, st)                               \
+   : r.mode == 2 ? launch_wgrad_tr<TN, TK, 2>(a, st) : launch_wgrad_tr<TN, TK, 0>(a, st))
+  if (r.tn == 64) return r.tk == 64 ? WG_TR(64, 64) : WG_TR(64, 128);
+  return r.tk == 64 ? WG_TR(128, 64) : WG_TR(128, 128);
 #undef WG_TR
 }
 
@@ -954,5 +965,13 @@ extern "C" int sdmi_wgrad_kernel(const SdmiWgradArgs* a, void*) {
   SDMI_REQUIRE(a, "null pointer");
   const char* err = wgrad_geometry_error(*a);
   SDMI_REQUIRE(!err, err);
-  return a->dtype == SDMI_BF16 ? select_wgrad_bf16(*a) : select_wgrad_f32(*a);
+  return (a->dtype == SDMI_BF16 ? select_wgrad_bf16(*a) : select_wgrad_f32(*a)).family;
+}
+
+extern "C" int sdmi_wgrad_route(const SdmiWgradArgs* a, void*) {
+  SDMI_REQUIRE(a, "null pointer");
+  const char* err = wgrad_geometry_error(*a);
+  SDMI_REQUIRE(!err, err);
+  const WgradRoute r = a->dtype == SDMI_BF16 ? select_wgrad_bf16(*a) : select_wgrad_f32(*a);
+  return r.family | (r.tn / 64) << 4 | (r.tk / 64) << 7 | r.mode << 10 | r.logw << 12;
 }
