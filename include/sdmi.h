@@ -374,7 +374,8 @@ int sdmi_layernorm_bwd(const SdmiLayerNormBwdArgs* a, void* stream);
 /* Deferred folds of the normalisation backward passes: up to 64 independent column sums
  *   out0[c] += sum_e partial[e][c][0],  out1[c] += sum_e partial[e][c][1]   (e < nblk)
  * in ONE launch (a train step has ~190 of them, each a few microseconds of work behind a launch).
- * `items` is a HOST array of n SdmiColsumItem. */
+ * `items` is a HOST array of n SdmiColsumItem.  out1 = NULL: `partial` is [nblk][C], one value per column (bias
+ * gradients from sdmi_rowgroup_sum partials): out0[c] += sum_e partial[e][c]. */
 typedef struct { const float* partial; float* out0; float* out1; int nblk, C; } SdmiColsumItem;
 typedef struct { const void* items; int n; } SdmiColsumGroupArgs;
 int sdmi_colsum_group(const SdmiColsumGroupArgs* a, void* stream);
@@ -957,7 +958,20 @@ int sdmi_mse(const SdmiMseArgs* a, void* stream);
  * ------------------------------------------------------------------------------------------ */
 /* dgrad operand: dst[ci][kh'][kw'][co] = src[co][KH-1-kh'][KW-1-kw'][ci]  (flip + transpose), so the
  * data gradient of a conv is sdmi_igemm on dY with this operand (pad' = K-1-pad, zins = stride). */
-typedef struct { const void* src; void* dst; int dtype; int Cout, KH, KW, Cin, CoutPad; } SdmiPackDgradArgs;
+/* Composite operands of an upsample convolution ("nearest 2x, then 3x3, pad 1", unet.py:108-121) trained as the
+ * ConvTranspose2d(k = 4, stride 2, padding 1) of the low-resolution input that it is.  Per dimension composite tap u =
+ * 0..3 gathers the source taps S[u] = {2}, {1,2}, {0,1}, {0}:
+ *   W4[co][ci][u][v] = sum over ky in S[u], kx in S[v] of src[co][ky][kx][ci]
+ * summed in fp32 with ky ascending and, inside one ky, kx ascending (((a + b) + c) + d), rounded to `dtype` ONCE.
+ *   SDMI_PACK_UPS_FWD    dst [4][Cout][2][2][Cin]: the `parity4` operand of sdmi_igemm -- tap (r, c) of output parity
+ *                        z = 2 py + px is W4[3 - 2r - py][3 - 2c - px];
+ *   SDMI_PACK_UPS_DGRAD  dst [Cin][4][4][CoutPad] = W4 with the channel roles swapped, taps NOT flipped: the data
+ *                        gradient is the plain 4x4 stride-2 pad-1 convolution of dY with it.
+ * Both need KH = KW = 3. */
+enum { SDMI_PACK_UPS_FWD = -1, SDMI_PACK_UPS_DGRAD = -2 };
+typedef struct { const void* src; void* dst; int dtype; int Cout, KH, KW, Cin, CoutPad;
+                 int comp;   /* 0, or SDMI_PACK_UPS_FWD / SDMI_PACK_UPS_DGRAD: a composite operand instead */
+} SdmiPackDgradArgs;
 /* dst row pitch CoutPad >= Cout (pad columns must be pre-zeroed by the caller) */
 int sdmi_pack_dgrad(const SdmiPackDgradArgs* a, void* stream);
 /* The same for a whole table of operands in ONE launch (every dgrad operand of the model is
@@ -970,7 +984,9 @@ typedef struct {
   int block_begin;
   /* optional tap selection (nkh > 0): dst holds only the taps kh' = kh0 + i*kstep (i < nkh),
    * kw' = kw0 + j*kstep (j < nkw) of the flipped filter, [Cin][nkh][nkw][CoutPad] -- the parity
-   * sub-filters of a strided convolution's data gradient; the operand takes nkh*nkw tap slices. */
+   * sub-filters of a strided convolution's data gradient; the operand takes nkh*nkw tap slices.
+   * kstep = SDMI_PACK_UPS_FWD / SDMI_PACK_UPS_DGRAD (nkh = nkw = 4, KH = KW = 3; kh0, kw0 unused): the composite
+   * operand of an upsample convolution instead (see SdmiPackDgradArgs), 16 tap slices. */
   int kh0, kw0, kstep, nkh, nkw;
 } SdmiPackDesc;
 typedef struct { const void* descs; int n_desc; int dtype; int total_blocks; } SdmiPackBatchArgs;
@@ -984,6 +1000,24 @@ int sdmi_rowgroup_sum(const SdmiRowGroupSumArgs* a, void* stream);
 /* y[b][y][x][c] = sum of the 2x2 block of x (backward of the nearest x2 upsample folded into a conv) */
 typedef struct { const void* x; void* y; int dtype; int B, H, W, C; } SdmiPool2x2Args;
 int sdmi_pool2x2_sum(const SdmiPool2x2Args* a, void* stream);
+/* Weight gradient of an upsample convolution from that of its composite 4x4 filter (SDMI_PACK_UPS_DGRAD's layout,
+ * fp32, as sdmi_wgrad writes it with the roles of x and dY swapped):
+ *   dw[co][ky][kx][ci] (+)= sum over (u, v) with ky in S[u], kx in S[v] of dw4[ci][u][v][co]
+ * -- u in {2 - ky, 3 - ky}, v in {2 - kx, 3 - kx}: four terms, summed u ascending and, inside one u, v ascending
+ * (((a + b) + c) + d).  A workgroup owns one tap of a 64 x 64 (co, ci) tile and transposes it through LDS: 16-byte
+ * accesses on both sides.  Cin % 4 == 0, Cout % 4 == 0.
+ * splits > 1: dw4 is the M-split workspace [splits][Cin * 16 * Cout] that sdmi_wgrad(defer_fold = 1) left; each of the
+ *   four terms is first the sum of its partials in split order (((p0 + p1) + p2) + ...).
+ * dy != NULL: extra workgroups of the same launch write the partials of the layer's bias gradient,
+ *   bias_part[g][co] = sum of the rows_per consecutive rows of group g of dY [rows][Cout] (`dtype`; rows % rows_per ==
+ *   0, Cout even) -- the sums of sdmi_rowgroup_sum's long-group kernel, bit for bit -- for sdmi_colsum_group (out1 =
+ *   NULL). */
+typedef struct {
+  const float* dw4; float* dw; int Cin, Cout; int accumulate;
+  int splits;
+  const void* dy; float* bias_part; int dtype, rows, rows_per;
+} SdmiUpsFoldArgs;
+int sdmi_ups_fold_dw(const SdmiUpsFoldArgs* a, void* stream);
 /* y = x + z elementwise in `dtype` (gradient accumulation at residual / skip joins) */
 typedef struct { const void* x; const void* z; void* y; int dtype; long long n; } SdmiAddArgs;
 int sdmi_add(const SdmiAddArgs* a, void* stream);

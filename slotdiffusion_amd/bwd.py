@@ -79,6 +79,16 @@ class LayerProblem(NamedTuple):
         Wo = (W - 1) * stride - 2 * pad + k + (stride - 1)
         return cls.conv(B, Ho, Wo, H, W, Cout, Cin, Cin, k, k, stride, (pad,) * 4, x.dtype)
 
+    @classmethod
+    def upsampled(cls, x, Cout):
+        """'Nearest 2x, then a 3x3 convolution, pad 1' on x [B, H, W, Cin] -> [B, 2H, 2W, Cout] is ConvTranspose2d(4,
+        stride 2, padding 1) with the composite filter W4 (sdmi.h: SDMI_PACK_UPS_*): the 4x4 stride-2 pad-1 convolution
+        [B, 2H, 2W, Cout] -> [B, H, W, Cin] with the roles swapped, as in `transposed` -- its forward IS the layer's data
+        gradient, its weight gradient (image dY, "output gradient" x, M = B H W low-resolution rows, K = 16 Cout) is
+        dW4 [Cin][4][4][Cout]."""
+        B, H, W, Cin = x.shape
+        return cls.conv(B, 2 * H, 2 * W, H, W, Cout, Cin, Cin, 4, 4, 2, (1, 1, 1, 1), x.dtype)
+
     # ---- argument-struct fields (pointers, splits / workspace and epilogue switches are the caller's) ----
     def wgrad_fields(self):
         """Scalar SdmiWgradArgs fields of dW[N][K] = dY^T im2col(x)."""
@@ -265,7 +275,7 @@ class GradSchedule:
         self._keep = []                   # rule 4
         self._pfold = None                # (SdmiWgradArgs fields, workspace) of the pending fold
         self._side_dst = {}               # destination pointer -> side stream with a launch into it in flight
-        self._cq = []
+        self._cq, self._cq_after = [], []
         self._groups = 0
         self._join_queued = False
 
@@ -380,13 +390,20 @@ class GradSchedule:
         self._keep.append(tuple(keep) + (ws,))
         self._ensure_join()
 
-    def queue_colsum(self, partial, nblk, C, out0, out1):
-        """Deferred dgamma / dbeta fold of a normalisation backward: launched, grouped, at the join."""
+    def queue_colsum(self, partial, nblk, C, out0, out1, after=None):
+        """Deferred dgamma / dbeta fold of a normalisation backward: launched, grouped, at the join.  out1 = None: one
+        column sum, partial [nblk][C] (a bias gradient).  after: the event behind the side-stream launch that writes
+        `partial` (the flush runs on the main stream before the side streams are joined)."""
         self._cq.append((partial, nblk, C, out0, out1))
+        if after is not None:
+            self._cq_after.append(after)
         self._ensure_join()
 
     def _flush_colsum(self):
         q, self._cq = self._cq, []
+        for ev in self._cq_after:
+            torch.cuda.current_stream().wait_event(ev)
+        del self._cq_after[:]
         # a parameter used several times per step (Slot Attention iterations, per-frame modules)
         # has several items with the same destination: they go to successive launches (the
         # workgroups of one launch read-modify-write their destinations concurrently)

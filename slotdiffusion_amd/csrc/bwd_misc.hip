@@ -14,6 +14,49 @@ static inline int nblocks(long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); \
        i += (long long)gridDim.x * blockDim.x)
 
+// Composite filter of an upsample convolution (sdmi.h: SDMI_PACK_UPS_*): composite tap u gathers the source taps
+// S[u] = {2}, {1,2}, {0,1}, {0} -- ups_s0(u) is the first of them, ups_sn(u) their number.
+__device__ __forceinline__ int ups_s0(int u) { return u == 0 ? 2 : (u == 1 ? 1 : 0); }
+__device__ __forceinline__ int ups_sn(int u) { return (u == 1 || u == 2) ? 2 : 1; }
+// slot = 4 z + 2 r + c of the parity4 operand -> (u, v) = (3 - 2r - py, 3 - 2c - px), z = 2 py + px
+__device__ __forceinline__ void ups_fwd_uv(int slot, int& u, int& v) {
+  const int z = slot >> 2, r = (slot >> 1) & 1, c = slot & 1;
+  u = 3 - 2 * r - (z >> 1);
+  v = 3 - 2 * c - (z & 1);
+}
+
+// one element of W4 [co][ci][u][v] from src [Cout][3][3][Cin]: fp32 sum, ky ascending, kx ascending inside one ky
+template <typename T>
+__device__ __forceinline__ float ups_w4(const T* src, int Cin, int co, int ci, int u, int v) {
+  float acc = 0.f;
+  for (int a = 0; a < ups_sn(u); ++a)
+    for (int b = 0; b < ups_sn(v); ++b) {
+      const float w = Elem<T>::ld(src + ((long long)co * 9 + (ups_s0(u) + a) * 3 + ups_s0(v) + b) * Cin + ci);
+      acc = (a | b) ? acc + w : w;
+    }
+  return acc;
+}
+
+template <typename T>
+__global__ void pack_ups_kernel(SdmiPackDgradArgs p) {
+  const long long n = 16LL * p.Cout * p.Cin;
+  GRID_STRIDE(i, n) {
+    if (p.comp == SDMI_PACK_UPS_DGRAD) {      // i indexes dst [ci][u][v][co]
+      const int co = (int)(i % p.Cout);
+      const long long r = i / p.Cout;
+      const int tap = (int)(r & 15), ci = (int)(r >> 4);
+      Elem<T>::st((T*)p.dst + r * p.CoutPad + co, ups_w4((const T*)p.src, p.Cin, co, ci, tap >> 2, tap & 3));
+    } else {                                  // i indexes dst [z][co][r][c][ci]
+      const int ci = (int)(i % p.Cin);
+      const long long q = i / p.Cin;
+      const int co = (int)((q >> 2) % p.Cout), z = (int)((q >> 2) / p.Cout);
+      int u, v;
+      ups_fwd_uv(z * 4 + (int)(q & 3), u, v);
+      Elem<T>::st((T*)p.dst + i, ups_w4((const T*)p.src, p.Cin, co, ci, u, v));
+    }
+  }
+}
+
 template <typename T>
 __global__ void pack_dgrad_kernel(SdmiPackDgradArgs p) {
   const long long n = (long long)p.Cout * p.KH * p.KW * p.Cin;
@@ -50,6 +93,52 @@ __global__ __launch_bounds__(256) void pack_dgrad_batch_kernel(SdmiPackBatchArgs
   w /= tci;
   const int co0 = (w % tco) * 64;
   const int tap = w / tco;                       // destination tap slot
+  if (d.kstep < 0) {                             // composite operand of an upsample convolution: 16 tap slots
+    const bool fwd = d.kstep == SDMI_PACK_UPS_FWD;
+    int u = tap >> 2, v = tap & 3;
+    if (fwd) ups_fwd_uv(tap, u, v);
+    const T* src = (const T*)d.src;
+    T* dst = (T*)d.dst;
+    for (int i = threadIdx.x; i < 64 * VPR; i += 256) {
+      const int r = i / VPR, c = (i % VPR) * VEC;  // r: co offset, c: ci offset
+      const int co = co0 + r, ci = ci0 + c;
+      float acc[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+      if (co < d.Cout && ci < d.Cin)
+        for (int a = 0; a < ups_sn(u); ++a)
+          for (int b = 0; b < ups_sn(v); ++b) {
+            const uint4 x = *reinterpret_cast<const uint4*>(
+                src + ((long long)co * 9 + (ups_s0(u) + a) * 3 + ups_s0(v) + b) * d.Cin + ci);
+            float f[VEC];
+            unpack16<T>(x, f);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) acc[j] = (a | b) ? acc[j] + f[j] : f[j];
+          }
+      const uint4 o = pack16<T>(acc);
+      if (fwd) {                                   // [z][co][r][c][ci]: no transpose
+        if (co < d.Cout && ci < d.Cin)
+          *reinterpret_cast<uint4*>(dst + (((long long)(tap >> 2) * d.Cout + co) * 4 + (tap & 3)) * d.Cin + ci) = o;
+      } else {
+        const T* e = reinterpret_cast<const T*>(&o);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) tile[r][c + j] = e[j];
+      }
+    }
+    if (fwd) return;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * VPR; i += 256) {
+      const int r = i / VPR, c = (i % VPR) * VEC;  // r: ci offset, c: co offset
+      const int ci = ci0 + r, co = co0 + c;
+      if (ci >= d.Cin || co >= d.CoutPad) continue;
+      uint4 o;
+      T* e = reinterpret_cast<T*>(&o);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) e[j] = tile[c + j][r];   // rows co >= Cout hold zeros
+      *reinterpret_cast<uint4*>(dst + ((long long)ci * 16 + tap) * d.CoutPad + co) = o;
+    }
+    return;
+  }
   const bool sel = d.nkh > 0;                    // tap selection (parity sub-filter) or the whole filter
   const int nkw = sel ? d.nkw : d.KW;
   const int ti = tap / nkw, tj = tap - ti * nkw;
@@ -105,11 +194,10 @@ __global__ __launch_bounds__(256) void rowgroup_sum_kernel(SdmiRowGroupSumArgs p
 // walk above is one latency-bound chain per thread; here a workgroup owns 64 columns (32 lanes x 2) and
 // its 8 row lanes stride the rows 8 loads deep, partial sums meet in LDS.  N and ldx even.
 template <typename T>
-__global__ __launch_bounds__(256) void rowgroup_sum_tall_kernel(SdmiRowGroupSumArgs p) {
+__device__ __forceinline__ void rowgroup_sum_tall_body(const SdmiRowGroupSumArgs& p, int bx, int g) {
   __shared__ float part[8][64];
   const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int n = blockIdx.x * 64 + 2 * cl;
-  const int g = blockIdx.y;
+  const int n = bx * 64 + 2 * cl;
   float s0 = 0.f, s1 = 0.f;
   if (n < p.N) {
     const T* x = (const T*)p.x + (long long)g * p.rows_per * p.ldx + n;
@@ -140,7 +228,7 @@ __global__ __launch_bounds__(256) void rowgroup_sum_tall_kernel(SdmiRowGroupSumA
   part[rl][2 * cl + 1] = s1;
   __syncthreads();
   if (threadIdx.x < 64) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
+    const int c = bx * 64 + threadIdx.x;
     if (c < p.N) {
       float t = 0.f;
 #pragma unroll
@@ -148,6 +236,10 @@ __global__ __launch_bounds__(256) void rowgroup_sum_tall_kernel(SdmiRowGroupSumA
       p.out[(long long)g * (p.ldo ? p.ldo : p.N) + c] = t;
     }
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void rowgroup_sum_tall_kernel(SdmiRowGroupSumArgs p) {
+  rowgroup_sum_tall_body<T>(p, blockIdx.x, blockIdx.y);
 }
 
 template <typename T>
@@ -395,6 +487,62 @@ __global__ __launch_bounds__(256) void adam_kernel(SdmiAdamArgs p) {
   }
 }
 
+// sdmi_ups_fold_dw: grid (ci tiles * co tiles, 9 taps + bias rows); a workgroup sums the four composite taps of its
+// (ky, kx) for a 64 (ci) x 64 (co) tile in registers -- u ascending, v ascending inside one u, each term first summed
+// over its M-split partials in split order -- and transposes the sum through LDS.  Rows y >= 9 of the grid are the bias
+// workgroups: workgroup b = (y - 9) * gridDim.x + x owns 64 columns of one row group of dY (rowgroup_sum_tall_body).
+__global__ __launch_bounds__(256) void ups_fold_dw_kernel(SdmiUpsFoldArgs p) {
+  if (blockIdx.y >= 9) {
+    const int cb = (p.Cout + 63) / 64, groups = p.rows / p.rows_per;
+    const int b = ((int)blockIdx.y - 9) * (int)gridDim.x + (int)blockIdx.x;
+    if (b >= cb * groups) return;
+    SdmiRowGroupSumArgs q = {};
+    q.x = p.dy; q.out = p.bias_part; q.groups = groups; q.rows_per = p.rows_per; q.N = p.Cout; q.ldx = p.Cout;
+    if (p.dtype == SDMI_BF16) rowgroup_sum_tall_body<bf16_t>(q, b % cb, b / cb);
+    else rowgroup_sum_tall_body<float>(q, b % cb, b / cb);
+    return;
+  }
+  __shared__ float tile[64][64 + 1];
+  const int tci = (p.Cin + 63) / 64;
+  const int ci0 = ((int)blockIdx.x % tci) * 64, co0 = ((int)blockIdx.x / tci) * 64;
+  const int ky = (int)blockIdx.y / 3, kx = (int)blockIdx.y % 3;
+  const int splits = p.splits > 1 ? p.splits : 1;
+  const long long nk = 16LL * p.Cin * p.Cout;
+  for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+    const int r = i >> 4, c = (i & 15) * 4;      // r: ci offset, c: co offset
+    const int ci = ci0 + r, co = co0 + c;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ci < p.Cin && co < p.Cout) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int u = 2 - ky + (t >> 1), v = 2 - kx + (t & 1);
+        const float* src = p.dw4 + ((long long)ci * 16 + u * 4 + v) * p.Cout + co;
+        float4 x = *reinterpret_cast<const float4*>(src);
+        for (int s = 1; s < splits; ++s) {
+          const float4 y = *reinterpret_cast<const float4*>(src + s * nk);
+          x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+        }
+        if (t == 0) acc = x;
+        else { acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w; }
+      }
+    }
+    tile[r][c] = acc.x; tile[r][c + 1] = acc.y; tile[r][c + 2] = acc.z; tile[r][c + 3] = acc.w;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+    const int r = i >> 4, c = (i & 15) * 4;      // r: co offset, c: ci offset
+    const int co = co0 + r, ci = ci0 + c;
+    if (co >= p.Cout || ci >= p.Cin) continue;
+    float4* o = reinterpret_cast<float4*>(p.dw + ((long long)co * 9 + blockIdx.y) * p.Cin + ci);
+    float4 s = make_float4(tile[c][r], tile[c + 1][r], tile[c + 2][r], tile[c + 3][r]);
+    if (p.accumulate) {
+      const float4 g = *o;
+      s.x += g.x; s.y += g.y; s.z += g.z; s.w += g.w;
+    }
+    *o = s;
+  }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -408,8 +556,29 @@ __global__ __launch_bounds__(256) void adam_kernel(SdmiAdamArgs p) {
 
 extern "C" int sdmi_pack_dgrad(const SdmiPackDgradArgs* a, void* stream) {
   SDMI_REQUIRE(a && a->src && a->dst && a->CoutPad >= a->Cout, "bad args");
+  if (a->comp) {
+    SDMI_REQUIRE((a->comp == SDMI_PACK_UPS_FWD || a->comp == SDMI_PACK_UPS_DGRAD) && a->KH == 3 && a->KW == 3,
+                 "composite operands: SDMI_PACK_UPS_FWD / SDMI_PACK_UPS_DGRAD of a 3x3 filter");
+    DISPATCH_T(pack_ups_kernel, dim3(nblocks(16LL * a->Cout * a->Cin)), a);
+    return sdmi_check_launch("pack_ups");
+  }
   DISPATCH_T(pack_dgrad_kernel, dim3(nblocks((long long)a->Cout * a->KH * a->KW * a->Cin)), a);
   return sdmi_check_launch("pack_dgrad");
+}
+extern "C" int sdmi_ups_fold_dw(const SdmiUpsFoldArgs* a, void* stream) {
+  SDMI_REQUIRE(a && a->dw4 && a->dw && a->Cin >= 4 && a->Cout >= 4 && a->Cin % 4 == 0 && a->Cout % 4 == 0 &&
+                   ((uintptr_t)a->dw4 % 16) == 0 && ((uintptr_t)a->dw % 16) == 0,
+               "Cin, Cout multiples of 4; 16-byte aligned pointers");
+  const int tiles = ((a->Cin + 63) / 64) * ((a->Cout + 63) / 64);
+  int extra = 0;
+  if (a->dy) {
+    SDMI_REQUIRE(a->bias_part && (a->dtype == SDMI_BF16 || a->dtype == SDMI_F32) && a->rows_per >= 1 && a->rows >= a->rows_per &&
+                     a->rows % a->rows_per == 0 && a->Cout % 2 == 0 && ((uintptr_t)a->dy % 8) == 0,
+                 "bias partials: rows a multiple of rows_per, Cout even");
+    extra = (int)(((long long)(a->rows / a->rows_per) * ((a->Cout + 63) / 64) + tiles - 1) / tiles);
+  }
+  hipLaunchKernelGGL(ups_fold_dw_kernel, dim3(tiles, 9 + extra), dim3(256), 0, ST, *a);
+  return sdmi_check_launch("ups_fold_dw");
 }
 extern "C" int sdmi_pack_dgrad_batch(const SdmiPackBatchArgs* a, void* stream) {
   SDMI_REQUIRE(a && a->descs && a->n_desc >= 1 && a->total_blocks >= 1, "bad args");

@@ -534,7 +534,11 @@ __global__ __launch_bounds__(256) void colsum_group_kernel(ColsumGroup g) {
   const int cl = threadIdx.x & 15, kg = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   float s0 = 0.f, s1 = 0.f;
-  if (c < C) {
+  const bool two = q_.out1 != nullptr;           // (else one value per column: sdmi.h)
+  if (c < C && !two) {
+    const float* q = q_.partial + c;
+    for (int k = kg; k < nblk; k += 16) s0 += q[(long long)k * C];
+  } else if (c < C) {
     const float2* q = reinterpret_cast<const float2*>(q_.partial) + c;
     int k = kg;
     for (; k + 48 < nblk; k += 64) {
@@ -557,7 +561,7 @@ __global__ __launch_bounds__(256) void colsum_group_kernel(ColsumGroup g) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) { a += red[k][cl][0]; b += red[k][cl][1]; }
     q_.out0[c] += a;
-    q_.out1[c] += b;
+    if (two) q_.out1[c] += b;
   }
 }
 
@@ -908,7 +912,7 @@ extern "C" int sdmi_colsum_group(const SdmiColsumGroupArgs* ga, void* stream) {
   g.n = ga->n;
   int cmax = 0;
   for (int i = 0; i < ga->n; ++i) {
-    SDMI_REQUIRE(it[i].partial && it[i].out0 && it[i].out1 && it[i].nblk >= 1 && it[i].C >= 1, "bad item");
+    SDMI_REQUIRE(it[i].partial && it[i].out0 && it[i].nblk >= 1 && it[i].C >= 1, "bad item");
     g.it[i] = it[i];
     if (it[i].C > cmax) cmax = it[i].C;
   }

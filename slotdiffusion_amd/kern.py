@@ -73,6 +73,7 @@ _WGRAD_HALO = bool(policy.flag('WGRAD_HALO'))    # direct 3x3 weight gradient on
 _CROSS_ONE = 64            # folded slot cross-attention as ONE launch (sdmi_cross_fold) up to this many tokens per image
 _ROLLOUT_FUSED = bool(policy.flag('ROLLOUT_FUSED'))   # fused SlotFormer rollout layer (sdmi_rollout_layer)
 _UPS_PARITY = bool(policy.flag('UPS_PARITY'))   # upsample convolutions as four 2x2 parity convolutions in one launch
+_UPS_TRAIN = policy.flag('UPS_PARITY') == 1     # ... and trained as the 4x4 stride-2 transposed convolutions they are
 # the fused inference block only when its grid (one workgroup per 64 / 32 token rows) fills a good part of the chip: at
 # B = 64 the 8^2 level gives 64 workgroups that each stream the block's 4 MB of weights -- 119 us against 108 us for the
 # per-layer launches (tests set these module variables)
@@ -396,6 +397,39 @@ def ups_parity_split(w):
     return out
 
 
+# The same layer as ONE transposed convolution: ConvTranspose2d(4, stride 2, padding 1) of the low-resolution input with
+# the composite filter W4 -- per dimension composite tap u gathers the source taps UPS_TAPS[u].  The training path
+# (GemmFn, WeightBank.ups_train_ok) makes its operands from W4 on the device (sdmi.h: SDMI_PACK_UPS_*) and folds dW4
+# back with sdmi_ups_fold_dw; the two functions below are the host restatement of those kernels, sums in their order.
+UPS_TAPS = ((2,), (1, 2), (0, 1), (0,))
+
+
+def ups_composite(w):
+    """w [Cout, Cin, 3, 3] -> W4 [Cout, Cin, 4, 4]: W4[.., u, v] = sum over ky in UPS_TAPS[u], kx in UPS_TAPS[v] of
+    w[.., ky, kx], ky ascending, kx ascending inside one ky, in w's dtype.  Tap (r, c) of parity (py, px) in
+    ups_parity_split is W4[.., 3 - 2r - py, 3 - 2c - px]."""
+    w4 = torch.empty(w.shape[:2] + (4, 4), dtype=w.dtype, device=w.device)
+    for u in range(4):
+        for v in range(4):
+            terms = [w[:, :, ky, kx] for ky in UPS_TAPS[u] for kx in UPS_TAPS[v]]
+            acc = terms[0]
+            for t in terms[1:]:
+                acc = acc + t
+            w4[:, :, u, v] = acc
+    return w4
+
+
+def ups_fold(dw4):
+    """dW4 [Cout, Cin, 4, 4] -> dw [Cout, Cin, 3, 3]: the transpose of ups_composite -- dw[.., ky, kx] = sum over (u, v)
+    with ky in UPS_TAPS[u], kx in UPS_TAPS[v] (u in {2 - ky, 3 - ky}), u ascending, v ascending inside one u."""
+    dw = torch.empty(dw4.shape[:2] + (3, 3), dtype=dw4.dtype, device=dw4.device)
+    for ky in range(3):
+        for kx in range(3):
+            a, b = 2 - ky, 2 - kx
+            dw[:, :, ky, kx] = ((dw4[:, :, a, b] + dw4[:, :, a, b + 1]) + dw4[:, :, a + 1, b]) + dw4[:, :, a + 1, b + 1]
+    return dw
+
+
 class WeightBank:
     """name(s) -> GEMM operand [N, K] in the requested dtype (K padded to the vector width)."""
 
@@ -438,8 +472,8 @@ class WeightBank:
 
     overlap_wgrad = property(lambda self: self.sched.overlap, lambda self, on: setattr(self.sched, 'overlap', bool(on)))
 
-    def queue_colsum(self, partial, nblk, C, out0, out1):
-        self.sched.queue_colsum(partial, nblk, C, out0, out1)
+    def queue_colsum(self, partial, nblk, C, out0, out1, after=None):
+        self.sched.queue_colsum(partial, nblk, C, out0, out1, after)
 
     def join_by_hand(self):
         """Backward kernels called outside an autograd pass: the caller calls join() itself."""
@@ -885,6 +919,32 @@ class WeightBank:
         names = names if not isinstance(names, str) else (names,)
         sub = (kh0, kw0, step, len(range(kh0, kh, step)), len(range(kw0, kw, step)))
         return self._dgrad(('dgradsub', names, dtype, kh0, kw0, step), names, dtype, kh, kw, cin_x, sub)
+
+    def ups_train_ok(self, x, wnames, geom, plain):
+        """An upsample convolution trained in the 4x4 stride-2 transposed form (GemmFn) -- the sampler's gate
+        (Kern.conv), on operands that come straight out of the shadow arena; `plain`: no rowvec / residual / out_dtype /
+        ldc.  The fp8 configuration keeps its layers as they are."""
+        kh, kw, stride, pad, ups = geom
+        if not (_UPS_TRAIN and ups and plain and isinstance(wnames, str) and (kh, kw, stride) == (3, 3, 1)
+                and tuple(pad) == (1, 1, 1, 1) and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0
+                and not getattr(self.model, 'fp8_unet', False)):
+            return False
+        p = self.t[wnames]
+        return p.dim() == 4 and p.shape[1] == x.shape[-1] and p.shape[0] % 8 == 0 and _grads_of(self, wnames) is not None
+
+    def ups_fwd(self, wname, dtype):
+        """Forward operand [4][Cout][2*2*Cin] of an upsample convolution in the transposed form (sdmi.h:
+        SDMI_PACK_UPS_FWD; ops.conv2d's parity4).  A member of the dgrad-operand table like `ups_wd`: both are re-made
+        from the shadow weights by the step's one sdmi_pack_dgrad_batch launch."""
+        co, ci = self.t[wname].shape[:2]
+        sub = (0, 0, _lib.ENUMS['SDMI_PACK_UPS_FWD'], 4, 4)
+        return self._dgrad(('upsfwd', (wname,), dtype), (wname,), dtype, 3, 3, ci, sub).view(4, co, 4 * ci)
+
+    def ups_wd(self, wname, dtype):
+        """... and its data-gradient operand [Cin][4*4*Cout] (SDMI_PACK_UPS_DGRAD): the weight of the 4x4 stride-2
+        pad-1 convolution dY -> dx."""
+        sub = (0, 0, _lib.ENUMS['SDMI_PACK_UPS_DGRAD'], 4, 4)
+        return self._dgrad(('upswd', (wname,), dtype), (wname,), dtype, 3, 3, self.t[wname].shape[1], sub)
 
     def _dgrad(self, key, names, dtype, kh, kw, cin_x, sub=None):
         m = self.dgrad_ops.get(key)
@@ -1398,7 +1458,16 @@ class GemmFn(torch.autograd.Function):
         w = wb.w(wnames, x.dtype)
         b = wb.b(bnames)
         x8 = getattr(x, '_sdmi_fp8', None)           # e4m3fn copy written by the GroupNorm in front (KernGrad.gn)
-        if x8 is not None and x8.shape == x.shape and wb.fp8_train_ok(x, wnames, geom):
+        ctx.ups4 = wb.ups_train_ok(x, wnames, geom, rowvec is None and residual is None and out_dtype is None
+                                   and ldc is None)
+        if ctx.ups4:
+            # nearest-2x upsample + 3x3 convolution = ConvTranspose2d(4, stride 2, padding 1) of the low-resolution input
+            # with the composite filter (sdmi.h: SDMI_PACK_UPS_*): four 2x2 parity convolutions in one launch here, a
+            # strided convolution of dY and a folded 4x4 weight gradient in backward -- 16 multiply-adds per output pixel
+            # and input channel instead of 36, all three ways
+            out = torch.empty((x.shape[0], 2 * x.shape[1], 2 * x.shape[2], w.shape[0]), dtype=x.dtype, device=x.device)
+            ops.conv2d(x, wb.ups_fwd(wnames, x.dtype), b, kh=2, kw=2, out=out, parity4=True)
+        elif x8 is not None and x8.shape == x.shape and wb.fp8_train_ok(x, wnames, geom):
             # e4m3fn operands in the forward GEMM: activations at the fixed scale of the inference path -- only where a
             # GroupNorm (+ SiLU) bounds them and wrote the operand itself: the stride-2 downsample convolutions read
             # the raw residual stream and keep bf16 in training -- weights at 448 / amax with amax taken on the device
@@ -1429,7 +1498,7 @@ class GemmFn(torch.autograd.Function):
             dalias = dalias.contiguous()
         wb, wnames, bnames, geom, has_rv, has_res, rv_shape = ctx.cfg
         dx, dy, (N, ldy, B, Ho, Wo, dt) = GemmFn.core(wb, x, dy, wnames, bnames, geom,
-                                                       ctx.needs_input_grad[0], dalias)
+                                                       ctx.needs_input_grad[0], dalias, ctx.ups4)
         drv = None
         if has_rv and ctx.needs_input_grad[1]:
             if ctx.rv_sink is not None:        # a column slice of the shared [B, total] gradient matrix
@@ -1450,9 +1519,10 @@ class GemmFn(torch.autograd.Function):
         return dx, drv, dres, None, None, None, None, None, None, None, None
 
     @staticmethod
-    def core(wb, x, dy, wnames, bnames, geom, need_dx, dalias=None):
+    def core(wb, x, dy, wnames, bnames, geom, need_dx, dalias=None, ups4=False):
         """Weight / bias gradient and data gradient of one conv / linear: build the problem, plan (bwd.plan_layer),
-        execute the plan.  -> (dx or None, dy in the compute dtype, (N, ldy, B, Ho, Wo, dt))."""
+        execute the plan.  -> (dx or None, dy in the compute dtype, (N, ldy, B, Ho, Wo, dt)).  ups4: the forward ran in
+        the transposed form (WeightBank.ups_train_ok)."""
         dt = x.dtype
         vec = ops.vec_of(dt)
         N = wb.w(wnames, dt).shape[0]
@@ -1461,6 +1531,8 @@ class GemmFn(torch.autograd.Function):
         if dy.dtype != dt or dy.shape[-1] % vec:
             npad = (N + vec - 1) // vec * vec
             dy = ops.cast2d(dy, dt, cols=N, ldd=npad)
+        if ups4:
+            return GemmFn._ups4(wb, x, dy, wnames, bnames, N, need_dx, dalias)
         P = bwd.LayerProblem.of(x, dy, geom, dt, N)
         info = (N, P.ldy, P.B, P.Ho, P.Wo, dt)
         # weight / bias gradients go straight into the gradient arena where it has the kernel's [N][K] layout
@@ -1527,6 +1599,42 @@ class GemmFn(torch.autograd.Function):
             sub = sub_of(a0, b0) if sub_of is not None else w4[:, a0::s, b0::s, :].contiguous()
             call('sdmi_igemm', _st(), a=_p(dy), w=_p(sub), out=_p(dx), split_k=1, residual=(_p(extra) if fuse else 0), **f)
         return dx, (None if fuse else extra)
+
+    @staticmethod
+    def _ups4(wb, x, dy, wname, bname, N, need_dx, dalias):
+        """Backward of an upsample convolution in the transposed form (bwd.LayerProblem.upsampled).  Main stream: dx =
+        the 4x4 stride-2 pad-1 convolution of dY with the composite operand, the gradient of x's other consumer in its
+        epilogue.  Side stream, two launches: dW4 [Cin][4][4][Cout] by sdmi_wgrad with the roles of x and dY swapped (its
+        M-split partials left in the workspace), then sdmi_ups_fold_dw, which folds them into the arena's
+        [Cout][3][3][Cin] and, with extra workgroups, writes the bias-gradient partials that the join folds with the
+        step's other column sums."""
+        dt = x.dtype
+        P = bwd.LayerProblem.upsampled(x, N)
+        dst = _grads_of(wb, wname)
+        bias = {}
+        if bname is not None:
+            rows = P.B * P.H * P.W
+            chunk = next((c for c in (256, 128, 64) if rows % c == 0), rows)
+            part = torch.empty((rows // chunk, N), dtype=torch.float32, device=x.device)
+            bias = dict(dy=_p(dy), bias_part=_p(part), dtype=_DT[dt], rows=rows, rows_per=chunk)
+        done = []
+
+        def wgrad():
+            splits = bwd.standalone_splits(P)
+            ws = torch.empty((splits * (P.N * P.K + P.N),), dtype=torch.float32, device=x.device)
+            call('sdmi_wgrad', _st(), a=_p(dy), dy=_p(x), dw=_p(ws), dbias=0, workspace=_p(ws), splits=splits,
+                 accumulate=0, defer_fold=1, **P.wgrad_fields())
+            call('sdmi_ups_fold_dw', _st(), dw4=_p(ws), dw=_p(dst), Cin=P.N, Cout=P.Cin, accumulate=1, splits=splits,
+                 **bias)
+            done.append(torch.cuda.Event())
+            done[0].record()
+        wb.sched.side_wgrad(wname, (_p(dst), 0), wgrad, (x, dy))
+        if bias:
+            wb.queue_colsum(part, rows // chunk, N, _grads_of(wb, bname), None, after=done[0])
+        dx = dalias
+        if need_dx:
+            dx = ops.conv2d(dy, wb.ups_wd(wname, dt), None, kh=4, kw=4, stride=2, pad=(1, 1, 1, 1), residual=dalias)
+        return dx, dy, (N, N, P.B, P.H, P.W, dt)
 
     @staticmethod
     def _wgrad(wb, x, dy, P, plan, names, bnames, dst, direct):

@@ -1,7 +1,7 @@
 """Kernel-selection policy in ONE place.
 
 Every switch of the product path is a row of `SWITCHES`: name -> (default, what it selects).  The environment can
-override a row for an A/B run (`SDMI_<NAME>=0/1`, read once at import); nothing else in the package reads the
+override a row for an A/B run (`SDMI_<NAME>=0/1`, `UPS_PARITY` also 2; read once at import); nothing else in the package reads the
 environment for kernel selection.  Measured choices that have no switch any more (the losing side was deleted) are
 listed in DESIGN.md's negatives ledger with their numbers."""
 import os
@@ -14,7 +14,9 @@ SWITCHES = {
     'LN_FOLD':       (1, 'LayerNorm folded into the linear layer behind it (bf16 inference)'),
     'RES_MERGE':     (1, 'ResBlock out_layers.3 + 1x1 skip convolution as one implicit GEMM'),
     'FF_MERGE':      (1, 'ff.net.2 + proj_out as one GEMM over [g | tok] with pre-multiplied weights'),
-    'UPS_PARITY':    (1, 'upsample convolutions as four 2x2 parity convolutions in one launch'),
+    'UPS_PARITY':    (1, 'upsample convolutions as four 2x2 parity convolutions in one launch -- 1: sampler and training '
+                         '(4x4 stride-2 transposed form: parity forward, strided data gradient, folded weight '
+                         'gradient), 2: sampler only, 0: off'),
     'DEFER_SPLITK':  (1, 'split-K second stage finished by the GroupNorm behind the convolution'),
     'LAZY_CAT':      (1, 'UNet skip concatenations read in place by their two consumers'),
     'ROLLOUT_FUSED': (1, 'fused SlotFormer rollout layer at inference (sdmi_rollout_layer: 2 launches instead of ~8)'),
