@@ -1170,6 +1170,29 @@ typedef struct {
   long long map_bstride, map_tstride;
 } SdmiSegTablesArgs;
 int sdmi_seg_tables(const SdmiSegTablesArgs* a, void* stream);
+/* Image-quality evaluation, the scoring tail of the reconstruction / video-prediction scripts in one launch: replaces,
+ * per batch of F frames, to_rgb_from_tensor of both images (utils.py:47-49), mse_metric / psnr_metric / ssim_metric
+ * (eval_utils.py:73-106) and the 8-bit frames the scripts save (img_based/test_recon.py:100-103).  pred and gt are
+ * fp32 in nominal [-1, 1], each either NCHW [F][3][H][W] (flag 0) or NHWC-4 [F][H][W][4] (flag 1: the decoder's rows;
+ * the fourth lane is never read).  With a = clamp(x * 0.5f + 0.5f, 0, 1) in fp32 (two roundings, no FMA):
+ *   se[f]   = sum over 3 * H * W of ((double)a_pred - (double)a_gt)^2
+ *   ssim[f] = mean over channels of the mean over the interior (5-pixel border cropped) of sdmi_ssim's expression
+ *             on (double)(a * 255.f), L = 255: 11-tap sigma = 1.5 window normalised in fp64, separable, rows first
+ *   u8      = (uint8) rintf(a * 255.f) (round half to even, np.round), [F][H][W][3]; pred_u8 / gt_u8 optional
+ * A workgroup owns one (frame, band of SSIM output rows); band j of frame f writes its fp64 partials
+ *   partial[f][j][0] = the squared error of the source rows the band owns (a partition of the H rows)
+ *   partial[f][j][1] = the band's SSIM sum / (3 * (H - 10) * (W - 10))
+ * and the caller adds the nbands partials of a frame in index order.  No floating-point atomics: two runs give the
+ * same bits, and every pixel enters se and the 8-bit frames exactly once whatever the band split.  nbands must be
+ * the kernel's own band count for (H, W) (metrics.img_quality_bands mirrors it).
+ * The gate: F >= 1, H >= 11, 11 <= W <= 256 (one thread per output column). */
+typedef struct {
+  const float* pred; const float* gt;
+  double* partial;                       /* [F][nbands][2] */
+  void* pred_u8; void* gt_u8;            /* [F][H][W][3] uint8, or NULL */
+  int F, H, W, pred_nhwc4, gt_nhwc4, nbands;
+} SdmiImgQualityArgs;
+int sdmi_img_quality(const SdmiImgQualityArgs* a, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

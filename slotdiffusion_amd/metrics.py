@@ -12,8 +12,11 @@ Attention's attention map into the tables directly (seg_tables), with one extra 
 map of COCO / VOC (img_based/models/eval_utils.py:119-135), and scores_from_tables does the arithmetic.  The five
 *_metric functions take the reference's optional third argument, inst_overlap_mask, through the same tables.
 
-Not covered: SSIM / LPIPS (skimage / lpips networks), bounding-box AP/AR (torchvision ops),
-postproc_mask.
+The image-quality stage (slotdiffusion_amd/quality.py) scores a batch of frames in one launch: image_quality ->
+sdmi_img_quality gives the per-frame squared error and SSIM of the to_rgb images and the 8-bit frames the reference
+saves, from NCHW images or the decoder's NHWC-4 rows; batch_quality turns the table into mse / psnr / ssim.
+
+Not covered: LPIPS (lpips networks), bounding-box AP/AR (torchvision ops), postproc_mask.
 """
 import numpy as np
 import torch
@@ -22,7 +25,8 @@ from . import _lib
 
 __all__ = ['contingency', 'adjusted_rand_index', 'ARI_metric', 'fARI_metric', 'miou_metric',
            'fmiou_metric', 'mbo_metric', 'mse_metric', 'psnr_metric', 'seg_tables', 'seg_tables_covers',
-           'overlap_tables', 'scores_from_tables', 'batch_scores']
+           'overlap_tables', 'scores_from_tables', 'batch_scores', 'to_rgb', 'image_quality', 'img_quality_covers',
+           'img_quality_bands', 'batch_quality']
 
 
 def _need_gpu(t):
@@ -325,6 +329,96 @@ def ssim_metric(x, y):
     _lib.call('sdmi_ssim', torch.cuda.current_stream().cuda_stream, x=xf.data_ptr(), y=yf.data_ptr(),
               out=out.data_ptr(), P=B * Cc, H=H, W=W, data_range=255.0)
     return float(out.view(B, Cc).mean(1).mean().cpu())        # mean over channels, then over images
+
+
+# ------------------------------------------------------------------------------------------
+# the scoring tail of the reconstruction / prediction scripts in one launch (sdmi_img_quality)
+# ------------------------------------------------------------------------------------------
+_IMG_QUALITY_FUSED = True          # tests and tools/bench_quality.py flip it: False sends image_quality down the composed path
+
+
+def to_rgb(x):
+    """to_rgb_from_tensor (utils.py:47-49): [-1, 1] -> [0, 1], clamped."""
+    return (x * 0.5 + 0.5).clamp(0, 1)
+
+
+def img_quality_covers(H, W):
+    """The gate of sdmi_img_quality (include/sdmi.h): an 11 x 11 window fits, one thread per output column."""
+    return bool(H >= 11 and 11 <= W <= 256)
+
+
+def img_quality_bands(H, W):
+    """The kernel's band split of (H, W) (img_quality.hip, iq_geom): up to 8 sub-bands of 8 SSIM output rows side by side
+    in the 256 threads, W - 10 rounded up to 32 threads each -> (output rows per band, bands per frame)."""
+    h, w = H - 10, W - 10
+    cw = (w + 31) // 32 * 32
+    s = max(1, min(8, 256 // cw, (h + 7) // 8))
+    return s * 8, (h + s * 8 - 1) // (s * 8)
+
+
+def image_quality(pred, gt, *, pred_nhwc4=False, gt_nhwc4=False, want_u8=(False, False), fused=None):
+    """MSE / PSNR / SSIM and the saved frames of a batch of F frames, as the reference's eval_imgs + save_results compute
+    them (eval_utils.py:73-106, img_based/test_recon.py:47-61, 94-103).  pred, gt: fp32 in nominal [-1, 1], each NCHW
+    [F, 3, H, W] or, with its flag, NHWC-4 [F, H, W, 4] (the decoder's rows: no transposition).  -> (table, pred_u8,
+    gt_u8): table fp64 [F, 2] on the device, (squared error of the to_rgb images summed over 3 * H * W, SSIM of the
+    frame); the uint8 frames [F, H, W, 3] that want_u8 = (pred, gt) asks for, None otherwise.  No host synchronisation:
+    mse / psnr / ssim of the batch are batch_quality(table.cpu(), 3 * H * W).
+
+    Inside img_quality_covers this is one sdmi_img_quality launch and a sum over its per-band partials; outside it, or
+    with fused=False (default: the module flag _IMG_QUALITY_FUSED), the composed path on the kernels behind mse_metric /
+    psnr_metric / ssim_metric with the same arithmetic."""
+    from . import ops
+    _need_gpu(pred)
+    _need_gpu(gt)
+    assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and pred.dim() == 4 and gt.dim() == 4
+
+    def hw(t, nhwc4):
+        if nhwc4:
+            assert t.shape[3] == 4, 'NHWC-4 rows are [F, H, W, 4]'
+            return t.shape[0], t.shape[1], t.shape[2]
+        assert t.shape[1] == 3, 'NCHW images are [F, 3, H, W]'
+        return t.shape[0], t.shape[2], t.shape[3]
+    F_, H, W = hw(pred, pred_nhwc4)
+    assert hw(gt, gt_nhwc4) == (F_, H, W), 'pred and gt hold the same frames'
+    if fused is None:
+        fused = _IMG_QUALITY_FUSED and img_quality_covers(H, W)
+    if fused:
+        pred, gt = pred.contiguous(), gt.contiguous()
+        if pred_nhwc4 and pred.data_ptr() % 16:
+            pred = pred.clone()
+        if gt_nhwc4 and gt.data_ptr() % 16:
+            gt = gt.clone()
+        _, nb = img_quality_bands(H, W)
+        part = torch.empty((F_, nb, 2), dtype=torch.float64, device=pred.device)
+        u8 = [torch.empty((F_, H, W, 3), dtype=torch.uint8, device=pred.device) if w else None for w in want_u8]
+        _lib.call('sdmi_img_quality', torch.cuda.current_stream().cuda_stream, pred=pred.data_ptr(), gt=gt.data_ptr(),
+                  partial=part.data_ptr(), pred_u8=u8[0].data_ptr() if u8[0] is not None else 0,
+                  gt_u8=u8[1].data_ptr() if u8[1] is not None else 0, F=F_, H=H, W=W, pred_nhwc4=int(pred_nhwc4),
+                  gt_nhwc4=int(gt_nhwc4), nbands=nb)
+        return part.sum(1), u8[0], u8[1]
+    a = to_rgb(ops.nhwc_to_nchw(pred.contiguous(), 3) if pred_nhwc4 else pred).contiguous()
+    b = to_rgb(ops.nhwc_to_nchw(gt.contiguous(), 3) if gt_nhwc4 else gt).contiguous()
+    st = torch.cuda.current_stream().cuda_stream
+    n = 3 * H * W
+    nchunk = max(1, min(64, n // 4096))
+    part = torch.empty((F_, nchunk), dtype=torch.float64, device=a.device)
+    _lib.call('sdmi_sqerr_rows', st, x=a.data_ptr(), y=b.data_ptr(), partial=part.data_ptr(), B=F_, n=n, nchunk=nchunk, mode=0)
+    xs, ys = (a * 255.0).contiguous(), (b * 255.0).contiguous()
+    planes = torch.empty((F_ * 3,), dtype=torch.float64, device=a.device)
+    _lib.call('sdmi_ssim', st, x=xs.data_ptr(), y=ys.data_ptr(), out=planes.data_ptr(), P=F_ * 3, H=H, W=W, data_range=255.0)
+    table = torch.stack([part.sum(1), planes.view(F_, 3).mean(1)], 1)
+    u8 = [torch.round(t).to(torch.uint8).permute(0, 2, 3, 1).contiguous() if w else None for t, w in zip((xs, ys), want_u8)]
+    return table, u8[0], u8[1]
+
+
+def batch_quality(table, n):
+    """The reference's values of one batch from its [F, 2] table (on the host) and n = 3 * H * W: mse = mean over frames
+    of the squared error (eval_utils.py:75-78), psnr = mean over frames of 10 log10(1 / (se / n)) (81-88), ssim = mean
+    over frames (91-106)."""
+    t = np.asarray(table, dtype=np.float64)
+    with np.errstate(divide='ignore'):
+        psnr = float(np.mean(10.0 * np.log10(1.0 / (t[:, 0] / n))))
+    return {'mse': float(t[:, 0].mean()), 'psnr': psnr, 'ssim': float(t[:, 1].mean())}
 
 
 def shuffle_slots(slots):

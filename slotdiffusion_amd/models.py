@@ -317,6 +317,16 @@ class LDM(_Owned):
         ret = self.generate_imgs(cond=cond, batch_size=B, ret_intermed=False, **kwargs)
         return {'samples': self.vae.decode(ret)}
 
+    @torch.no_grad()
+    def sample_rows(self, batch, **kwargs):
+        """log_images' samples as the VQ-VAE decoder leaves them, for the image-quality stage (quality.py):
+        -> (rows [B, H, W, 4] fp32 NHWC-4, True).  The same launches as log_images without the transposition to NCHW;
+        metrics.image_quality(pred_nhwc4=True) reads the rows as they are."""
+        cond = batch[self.cond_stage_key]
+        z = self.generate_imgs(cond=cond, batch_size=cond.shape[0], ret_intermed=False, **kwargs)
+        r = self.root
+        return engine.vae_decode(r.K(), r._latent_nhwc(z), r.ed, scale_factor=r.z_scale, quantize=True), True
+
 
 class CondDDPM(LDM):
     """`model.dm_decoder` of a dec_dict without `vae_dict` (cond_ddpm.py:21-240): the same slot-conditioned UNet run
@@ -349,6 +359,12 @@ class CondDDPM(LDM):
             raise ValueError('ret_intermed=True: the diffusion / denoise rows of log_images are torchvision grids, not built')
         cond = batch[self.cond_stage_key]
         return {'samples': self.generate_imgs(cond=cond, batch_size=cond.shape[0], ret_intermed=False, **kwargs)}
+
+    @torch.no_grad()
+    def sample_rows(self, batch, **kwargs):
+        """LDM.sample_rows on the image-space decoder: the sampled state is the image, which generate_imgs returns as
+        NCHW -> (samples [B, 3, H, W] fp32, False)."""
+        return self.log_images(batch, **kwargs)['samples'], False
 
 
 def _decoder_nodes(dec_dict, who):
