@@ -759,6 +759,33 @@ typedef struct {
 int sdmi_readout_bwd(const SdmiReadoutBwdArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Physion VQA test stage (vp_vqa/test_physion_vqa.py: the sweep over checkpoints and thresholds): a bank of W readouts
+ * of one geometry and K thresholds scored on a batch of videos in ONE launch -- a workgroup per (video, checkpoint)
+ * walks the video's frames through sdmi_readout_fwd's arithmetic, keeps the time max in a register, and K lanes count
+ * the correct decisions per task.  No workspace, no memset, no copy.
+ *   slots [B][T][N][C] contiguous, x_dtype fp32 or bf16, 16-byte aligned; rounded to op_dtype on load.
+ *   w1p [W][F 2C] in op_dtype: checkpoint w's linear1.weight packed exactly as sdmi_readout_fwd's w1p
+ *     (kern.readout_pack_index), 16-byte aligned;  b1 [W][F], w2 [W][F], b2 [W] fp32.  agg: 0 sum, 1 mean, 2 max.
+ *   label [B] fp32 (0 or 1), task [B] int32 in [0, J) (a sample outside is counted nowhere), cut [K] fp32: thresholds
+ *     in LOGIT space.
+ *   logits [W][B] fp32: logits[w][b] has the bit pattern sdmi_readout_fwd's logits[b] has with checkpoint w's operands,
+ *     for both operand dtypes (same k order in the MFMA chain, same rounding points, the aggregate in the same type,
+ *     linear2's F-term sum in fp64 in the same order, the same tie rule in the time max).
+ *   correct [W][K][J] int32: correct[w][k][task[b]] += ((logits[w][b] > cut[k]) == (label[b] != 0)); the comparison is
+ *     strict.  The kernel ADDS to the table and never clears it: the host zeroes it once per evaluation (the convention
+ *     of sdmi_seg_tables).  Integer atomics only: the result does not depend on execution order.
+ *   2 <= N <= 16; C, F multiples of 32 up to 256; T, B >= 1; 1 <= W <= 65535; 1 <= K <= 32; 1 <= J <= 64
+ *     (SDMI_EINVAL outside: the caller runs the composed stage, slotdiffusion_amd/vqa.py).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* slots; const void* w1p; const float* b1; const float* w2; const float* b2;
+  const float* label; const int* task; const float* cut;
+  float* logits; int* correct;
+  int B, T, N, C, F, W, K, J, agg, x_dtype, op_dtype;
+} SdmiVqaScoreArgs;
+int sdmi_vqa_score(const SdmiVqaScoreArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training twin of the fused SpatialTransformer block (bf16): the forward pass of
  * SpatialTransformer.forward / BasicTransformerBlock._forward / CrossAttention.forward / FeedForward
  * (video_based/models/unet/attention.py:297-308, 247-251, 182-206, 44-65) in TWO launches that also store

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, '..', 'libsdmi.so')
 SOURCES = ['api.cpp', 'igemm.hip', 'igemm_halo.hip', 'wgrad.hip', 'bwd_pair.hip', 'norm.hip', 'norm_bwd.hip', 'attention.hip',
-           'attention_bwd.hip', 'st_fused.hip', 'rollout_layer.hip', 'readout.hip', 'slot_pred.hip', 'st_train.hip', 'cross_fold.hip', 'slot_attn.hip', 'slot_attn_train.hip', 'bwd_misc.hip',
+           'attention_bwd.hip', 'st_fused.hip', 'rollout_layer.hip', 'readout.hip', 'vqa_score.hip', 'slot_pred.hip', 'st_train.hip', 'cross_fold.hip', 'slot_attn.hip', 'slot_attn_train.hip', 'bwd_misc.hip',
            'elementwise.hip', 'vq.hip', 'dpm_px.hip', 'metrics.hip', 'seg_eval.hip', 'img_quality.hip', 'vae_train.hip']
 EXTRA = {'vq.hip': ['-ffp-contract=off'], 'elementwise.hip': ['-ffp-contract=off'], 'dpm_px.hip': ['-ffp-contract=off'],
          'seg_eval.hip': ['-ffp-contract=off'],        # the upsample of elementwise.hip's mask_up_kernel, bit for bit

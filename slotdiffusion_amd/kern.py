@@ -199,6 +199,9 @@ def rollout_index_b(C, F):
 # rest, and everything with this off (tests, tools/bench_readout.py), runs engine.readout_composed.  Not a policy
 # switch: the choice is geometric.
 _READOUT_FUSED = True
+# The VQA test stage (slotdiffusion_amd/vqa.py) on sdmi_vqa_score wherever readout_covers and vqa_score_covers hold; the
+# rest, and everything with this off (tests, tools/bench_vqa_test.py), runs the composed stage.  Geometric as well.
+_VQA_FUSED = True
 READOUT_AGG = {'sum': _lib.ENUMS['SDMI_AGG_SUM'], 'mean': _lib.ENUMS['SDMI_AGG_MEAN'], 'max': _lib.ENUMS['SDMI_AGG_MAX']}
 _READOUT_INDEX = {}
 
@@ -206,6 +209,11 @@ _READOUT_INDEX = {}
 def readout_covers(N, C, F):
     """Geometry of sdmi_readout_fwd / sdmi_readout_bwd (sdmi.h)."""
     return 2 <= N <= 16 and 32 <= C <= 256 and C % 32 == 0 and 32 <= F <= 256 and F % 32 == 0
+
+
+def vqa_score_covers(N, C, F, W, K, J):
+    """Geometry of sdmi_vqa_score (sdmi.h): the readout's, and the bank / threshold / task counts."""
+    return readout_covers(N, C, F) and 1 <= W <= 65535 and 1 <= K <= 32 and 1 <= J <= 64
 
 
 def readout_pack_index(C, F, dtype, device='cpu'):

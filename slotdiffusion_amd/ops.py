@@ -890,6 +890,36 @@ def readout_fwd(slots, w1p, b1, w2, b2, agg, op_dtype, label=None, loss_weight=1
     return dict(frame_logits=frame_logits, logits=logits, t_star=t_star, loss=loss, dlogit=dlogit)
 
 
+def vqa_score(slots, w1p, b1, w2, b2, agg, op_dtype, label, task, cut, num_tasks, correct=None):
+    """sdmi_vqa_score: slots [B, T, N, C] (fp32 / bf16), a bank of W readouts -- w1p [W, F * 2C] in op_dtype (each row
+    packed by kern.readout_pack_index), b1 [W, F], w2 [W, F], b2 [W] fp32 -- label [B] (0 / 1), task [B] in
+    [0, num_tasks), cut [K] fp32 (logit space) -> (logits [W, B] fp32, correct [W, K, num_tasks] int32).  The launch ADDS
+    to `correct` (a zeroed table is made when none is given): pass the same table for every batch of an evaluation."""
+    _need_gpu(slots, w1p)
+    slots = slots.contiguous()
+    B, T, N, C = slots.shape
+    W, F = b1.shape
+    dev = slots.device
+    assert w1p.shape == (W, F * 2 * C) and w1p.dtype == op_dtype and w1p.is_contiguous()
+    assert w2.shape == (W, F) and b2.shape == (W,)
+    b1, w2, b2 = (t.float().contiguous() for t in (b1, w2, b2))
+    label = label.reshape(-1).float().contiguous()
+    task = task.reshape(-1).to(torch.int32).contiguous()
+    cut = cut.reshape(-1).float().contiguous()
+    assert label.numel() == B and task.numel() == B
+    K, J = cut.numel(), int(num_tasks)
+    if correct is None:
+        correct = torch.zeros((W, K, J), dtype=torch.int32, device=dev)
+    assert correct.shape == (W, K, J) and correct.dtype == torch.int32 and correct.is_contiguous()
+    logits = torch.empty((W, B), dtype=torch.float32, device=dev)
+    call('sdmi_vqa_score', _stream(), slots=_p(slots), w1p=_p(w1p), b1=_p(b1), w2=_p(w2), b2=_p(b2), label=_p(label),
+         task=_p(task), cut=_p(cut), logits=_p(logits), correct=_p(correct), B=B, T=T, N=N, C=C, F=F, W=W, K=K, J=J,
+         agg=_agg(agg), x_dtype=_dt(slots), op_dtype=_DT[op_dtype],
+         _meta=dict(flops=4.0 * W * B * T * N * C * F,
+                    bytes=float(slots.numel() * slots.element_size() + w1p.numel() * w1p.element_size() + 4 * W * B)))
+    return logits, correct
+
+
 def readout_finish(frame_logits, label=None, loss_weight=1.0):
     """The finisher launch alone: frame_logits [B, T] fp32 -> max over time, t_star, BCE-with-logits and dlogit."""
     _need_gpu(frame_logits)

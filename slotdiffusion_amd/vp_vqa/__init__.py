@@ -6,6 +6,7 @@ from .. import models as _models
 from ..method import (SlotsFileDataModule, SlotsLabelFileDataModule, SyntheticSlotsDataModule,  # noqa: F401
                       SyntheticSlotsLabelDataModule, build_method)
 from ..quality import evaluate_video_prediction  # noqa: F401
+from ..vqa import (PhysionVQATestSet, ReadoutBank, evaluate_physion_vqa, format_report, logit_cuts)  # noqa: F401
 
 # the labels of the two Physion subsets under params.data_root (vp_vqa/datasets/physion.py:250-253)
 PHYSION_LABELS = {'readout': 'PhysionTrainMP4s/readout_labels.csv', 'test': 'PhysionTestMP4s/labels.csv'}
