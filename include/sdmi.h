@@ -1220,6 +1220,50 @@ typedef struct {
   int F, H, W, pred_nhwc4, gt_nhwc4, nbands;
 } SdmiImgQualityArgs;
 int sdmi_img_quality(const SdmiImgQualityArgs* a, void* stream);
+/* Slot-decomposition panel of the validation pass, from masks and frames straight to the 8-bit make_grid picture in one
+ * launch: replaces, per F frames, the argmax over slots and torch_draw_rgb_mask (video_based/vis.py:18-45), the masked
+ * tiles and their concatenation (img_based/method.py:91-108, 288-318; video_based/method.py:104-130, 344-369),
+ * make_one_hot for the hard panel (video_based/method.py:413; steve_utils.py:10-17), F.one_hot for the ground-truth
+ * panel (video_based/method.py:419-421), vutils.make_grid(nrow = tiles, padding 2, pad_value = -1) per frame and
+ * to_rgb_from_tensor, * 255, astype(uint8) (img_based/method.py:31-44, video_based/method.py:50-57).
+ * Inputs, F frames of H x W: img fp32 NCHW [F][3][H][W] (img_nhwc4 = 0) or NHWC-4 [F][H][W][4] (1; the fourth lane is
+ * never read); recon (optional) likewise with recon_nhwc4; exactly one mask source --
+ *   seg  fp32 soft masks: seg_planar = 0: [F][h*w][N] as sdmi_slot_attention writes them (16-byte aligned);
+ *        seg_planar = 1: planar [F][N][h][w] (the alpha masks of SA / SAVi, h == H)
+ *   ids  int32 [F][H][W]: the ground-truth panel, N = the class count --
+ * gt (optional) int32 [F][H][W], read by GTCOLOR tiles only; slot_img (optional) fp32 [F][N][3][H][W], the per-slot
+ * reconstructions the slot tiles show in place of img; palette fp32 [P][3] in [-1, 1].
+ * A frame's tiles are the nprefix <= 8 codes of `tiles` (4 bits each, tile j in bits 4 j .. 4 j + 3: 0 IMG, 1 RECON,
+ * 2 COLOR, 3 OVERLAY, 4 GTCOLOR) followed by the N slot tiles.  Per pixel, all in fp32 with every product and sum
+ * rounded on its own (the file is compiled without FMA contraction): m_k = the bilinear upsample (align_corners=False)
+ * of slot k in the arithmetic of sdmi_mask_upsample_argmax expression for expression (any ratio H/h, W/w; the source
+ * value itself when h == H, w == W), or (ids == k) ? 1 : 0; a = argmax_k m_k with strict > (the lowest index wins a
+ * tie), or the id; v = the image pixel, r = recon's, s = slot_img[f][k] when given, else v.  Tile values:
+ *   IMG v_c;  RECON r_c;  COLOR pal[a][c];  OVERLAY v_c * 0.7f + pal[a][c] * (float)(1.0 - 0.7);  GTCOLOR pal[gt][c];
+ *   slot k, soft panel: s_c * m_k + (1.f - m_k);   hard panel: the same with m_k := (k == a) ? 1.f : 0.f
+ *   byte = (uint8)(clamp(t * 0.5f + 0.5f, 0, 1) * 255.f)   (a truncation)
+ * An id outside [0, N) (ids) or [0, P) (gt) draws byte 0 in the colour tiles and belongs to no slot tile (our rule: the
+ * reference would raise).  Inputs are finite.
+ * Outputs: `soft` and (optional) `hard`, uint8, both written by the one launch with the same strides.  Frame f goes to
+ * picture f / G, tile row f % G (G = 1: the video form, one picture per frame; G = F: the image form); a picture is
+ * GH x GW = (G (H + 2) + 2) x ((nprefix + N) (W + 2) + 2) per channel and byte (picture i, channel c, row y, column x)
+ * is at  i * img_stride + c * ch_stride + y * row_stride + x  (strides in bytes, so a video's panel can be a band of
+ * rows of a taller picture).  EVERY byte of the rectangles is written (padding = 0, what pad_value -1 becomes), none
+ * outside them: no memset or host fill is needed.
+ * The gate: N >= 1; h, w, H, W >= 1; F a multiple of G; N <= P when a COLOR or OVERLAY tile is asked for; the strides
+ * keep rows, planes and pictures apart; 3 panel rows, the id row and the source rows of a band of one output row
+ * must fit 160 KiB of LDS (SDMI_EUNSUPPORTED otherwise: vis.slot_panel_covers mirrors it, and the host then runs the
+ * composed path; no shape this project configures is near it). */
+typedef struct {
+  const float* img; const float* recon; const float* seg; const int* ids; const int* gt;
+  const float* slot_img; const float* palette;
+  void* soft; void* hard;
+  int F, G, N, P, H, W, h, w;
+  int img_nhwc4, recon_nhwc4, seg_planar, nprefix;
+  unsigned tiles;
+  long long img_stride, ch_stride, row_stride;
+} SdmiSlotPanelArgs;
+int sdmi_slot_panel(const SdmiSlotPanelArgs* a, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -8,10 +8,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, '..', 'libsdmi.so')
 SOURCES = ['api.cpp', 'igemm.hip', 'igemm_halo.hip', 'wgrad.hip', 'bwd_pair.hip', 'norm.hip', 'norm_bwd.hip', 'attention.hip',
            'attention_bwd.hip', 'st_fused.hip', 'rollout_layer.hip', 'readout.hip', 'vqa_score.hip', 'slot_pred.hip', 'st_train.hip', 'cross_fold.hip', 'slot_attn.hip', 'slot_attn_train.hip', 'bwd_misc.hip',
-           'elementwise.hip', 'vq.hip', 'dpm_px.hip', 'metrics.hip', 'seg_eval.hip', 'img_quality.hip', 'vae_train.hip']
+           'elementwise.hip', 'vq.hip', 'dpm_px.hip', 'metrics.hip', 'seg_eval.hip', 'img_quality.hip', 'slot_panel.hip', 'vae_train.hip']
 EXTRA = {'vq.hip': ['-ffp-contract=off'], 'elementwise.hip': ['-ffp-contract=off'], 'dpm_px.hip': ['-ffp-contract=off'],
          'seg_eval.hip': ['-ffp-contract=off'],        # the upsample of elementwise.hip's mask_up_kernel, bit for bit
          'img_quality.hip': ['-ffp-contract=off'],     # to_rgb and the * 255 of the composed path: two roundings each
+         'slot_panel.hip': ['-ffp-contract=off'],      # mask_up_kernel's upsample bit for bit; tile products rounded singly
          # no packed-fp32 VALU ops in the fused training kernels (st_train.hip's build note: not repeatable on MI355X)
          'st_train.hip': ['-fno-slp-vectorize'],
          # shares st_core.h's helpers with st_train.hip: built the same way until that note is explained

@@ -225,6 +225,12 @@ class Method:
         self.use_graph = os.environ.get('SDMI_GRAPH', '1') != '0'
         self.optimizer = None
         self.history = []
+        self.epoch = 0                    # the epoch being trained, counted from 1 (0: before fit)
+        self.val_history = []             # (step, log) per validation pass, kept by the default log_fn
+        self.log_fn = self._keep_log
+
+    def _keep_log(self, log, step=None):
+        self.val_history.append((step, log))
 
     def _get(self, key, default=None):
         p = self.params
@@ -283,12 +289,16 @@ class Method:
         if ckp is not None:
             self._restore_training_state(ckp)
         graphed = None
+        validating = hasattr(self.datamodule, 'val_loader')
+        if validating and san_check_val_step > 0:
+            self.validate(san_check_step=san_check_val_step)
         steps_per_epoch = len(self.datamodule)
         first_epoch = self.it // max(1, steps_per_epoch)
         # a mid-epoch checkpoint resumes BEHIND the batches it already consumed: the run then sees the
         # same batch sequence, and executes exactly max_epochs * steps_per_epoch steps in total
         skip = self.it - first_epoch * steps_per_epoch
         for epoch in range(first_epoch, self.params.max_epochs):
+            self.epoch = epoch + 1
             for bi, batch in enumerate(self.datamodule.train_loader(epoch)):
                 if epoch == first_epoch and bi < skip:
                     continue
@@ -307,7 +317,31 @@ class Method:
                 self.model._training_step_end(self)
                 if max_steps is not None and self.it >= max_steps:
                     return self
+            if validating and (self.epoch % (self._get('eval_interval', 1) or 1) == 0 or
+                               self.epoch == self.params.max_epochs):
+                self.validate()
         return self
+
+    def validate(self, san_check_step=-1, sample=True):
+        """One validation pass (SlotBaseMethod.validation_epoch of both reference method.py files, with the
+        `_sample_img` / `_sample_video` of the model's method class) -> the logged dict, also sent to
+        `self.log_fn(log, step=self.it)`, whose default appends (step, log) to `self.val_history`.
+
+        The model is put in eval mode without gradients.  Every batch of `datamodule.val_loader()` goes through
+        `model.calc_eval_loss(batch, model(batch))`; each key is averaged WEIGHTED BY BATCH SIZE into `val/<key>`
+        (nerv's own loop is not part of the reference tree: the weighting is this project's decision, so that a short
+        last batch counts by its samples), stopping after `san_check_step` batches when that is > 0.  With use_ddp the
+        per-key sums and the count are all-reduced in one tensor.  On rank 0, with `sample` and a `datamodule.val_set`,
+        the model's samples follow (validate.py): the DPM reconstruction loss at the end of an epoch
+        (san_check_step <= 0; for videos also in the last epoch) and the slot-decomposition panels, as uint8 numpy
+        arrays -- [H, W, 3] for an image, [T, 3, H, W] for a video, what wandb.Image / wandb.Video take.
+        `params.val_sampler_kwargs` (optional, default {}) is forwarded to the sampler calls, e.g. dpm_steps.
+
+        Training is not moved: torch's generator states and the model's training / testing flags are restored, the
+        sampler noise comes from a generator seeded by (seed, self.it), and the inference operands are refreshed from
+        the weights of the step just taken.  Only the model's eval_seed stream advances."""
+        from .validate import run_validation
+        return run_validation(self, san_check_step, sample)
 
     def _loss_names(self):
         from .models import SA, VQVAE
